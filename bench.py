@@ -1,6 +1,6 @@
 """Benchmark of the W-HMR hot path on MI355X.  Contract: see the task brief / DESIGN.md "Measurement".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload vit224|vit256x192|vitl256x192|whmr|whmr_train] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload vit224|vit256x192|vitl256x192|whmr|whmr_train] [--no-cpu] [--dump-outputs DIR]
 
 A step = one forward of the hot path over one batch of 64 synthetic crops per GPU (inputs resident in HBM).
 N=1 default workload = BASELINE.json configs[1]: ViT-B/16 backbone only, 224x224, batch 64, bf16 MFMA.
@@ -72,7 +72,13 @@ def parse(argv=None):
                     help='default run (vit224, 1 GPU): skip the short secondary legs (the same workload in bf16x3, BASELINE configs[2] whmr, configs[3] whmr_train)')
     ap.add_argument('--rank-timeout', type=float, default=1500.0,
                     help='launcher: seconds after which the child ranks are killed (process group) and the launcher exits 124; also the collective timeout')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy in float32 / float64, at most 64 MB in all '
+                         '(larger arrays as a fixed, seeded sample of their flat elements): two builds run with the same arguments compare output for output')
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def build_workload(args, dev):
@@ -125,7 +131,11 @@ def build_workload(args, dev):
         if args.eager:
             return eager, None, inp['x'], (256, 192)
         g = GraphedForward(m, *a, **kw)
-        return (lambda: g.graph.replay()), None, inp['x'], (256, 192)
+
+        def graph_replay():
+            g.graph.replay()
+            return g.out                                    # the graph's static outputs, rewritten by every replay
+        return graph_replay, None, inp['x'], (256, 192)
     if args.workload == 'whmr_train':
         # BASELINE configs[3] (train.py pymaf_net step, batch 64 per GPU, DP gradient all-reduce over RCCL): forward in training mode,
         # a synthetic L2 loss on the tensors core/trainer.py:500-600 supervises, backward through the HIP autograd nodes, bucketed
@@ -251,14 +261,16 @@ def build_workload(args, dev):
             finally:
                 WT.OVERLAP_HEAVY = ov
         args.eager_step = train_step_serial
+        args.dump_tree = lambda loss: {'loss': loss, 'grad': {n: p.grad for n, p in named}}
         if use_graph:
             from whmr_amd.train import capture_train_step
             with torch.enable_grad():
-                replay, _ = capture_train_step(m, fwd_bwd)       # forward + backward replayed; the optimizer step stays eager
+                replay, graph_loss = capture_train_step(m, fwd_bwd)       # forward + backward replayed; the optimizer step stays eager
 
             def graph_step():
                 replay()
                 opt.step()
+                return graph_loss
             return graph_step, None, inp['x'], (256, 192)
         return train_step, None, inp['x'], (256, 192)
     raise SystemExit('unknown workload %s' % args.workload)
@@ -380,6 +392,43 @@ def time_steps(step, steps, warmup):
         step()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps * 1e3
+
+
+def _named_tensors(obj, name, out):
+    if torch.is_tensor(obj):
+        out[name or 'output'] = obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            _named_tensors(v, '%s.%s' % (name, k) if name else str(k), out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _named_tensors(v, '%s.%d' % (name, i) if name else str(i), out)
+    return out
+
+
+def dump_outputs(tree, path, budget=60 << 20):
+    """the tensors of ``tree`` (nested dicts / lists) as path/<dotted name>.npy: float64 and integer tensors as float64, the rest as float32.
+    Within ``budget`` bytes of array data (60 MiB: the files' headers stay inside 64 MB): the smaller arrays whole, each larger one cut to an equal
+    share of what is left, a sample of its flat elements at indices drawn from a generator seeded 0 (sorted) -- the same elements in every run
+    of the same arguments."""
+    import numpy as np
+    arrays = {}
+    for n, t in _named_tensors(tree, '', {}).items():
+        exact64 = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        arrays[n] = (t.detach().double() if exact64 else t.detach().float()).cpu()
+    os.makedirs(path, exist_ok=True)
+    left, files = budget, {}
+    order = sorted(arrays, key=lambda n: arrays[n].numel() * arrays[n].element_size())
+    for i, n in enumerate(order):
+        a = arrays[n]
+        keep = min(a.numel(), (left // (len(order) - i)) // a.element_size())
+        if keep < a.numel():
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.reshape(-1)[idx]
+        left -= a.numel() * a.element_size()
+        np.save(os.path.join(path, n.replace(os.sep, '_') + '.npy'), a.numpy())
+        files[n] = {'shape': list(arrays[n].shape), 'dtype': str(a.dtype).replace('torch.', ''), 'sampled': keep < arrays[n].numel()}
+    return {'dir': path, 'bytes': budget - left, 'arrays': files}
 
 
 def observed_clock(step, dev, n):
@@ -1020,8 +1069,9 @@ def main(argv=None):
             red.timing, red._wait_marks = True, []
             red.stats = {k: 0 for k in red.stats}
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             step()
+        last = step()
         sync()
         dt_own = time.perf_counter() - t0                # this rank's own time, before it waits for the others
         barrier()
@@ -1029,6 +1079,10 @@ def main(argv=None):
         if red is not None:
             red.timing = False
             args.reducer_stats = dict(red.stats)     # snapshot: the instrumented step below also exchanges gradients
+        dumped = None
+        if args.dump_outputs and rank == 0:          # before the instrumented step below rewrites graph outputs and gradients
+            dumped = dump_outputs(getattr(args, 'dump_tree', lambda out: out)(last), args.dump_outputs)
+        del last
         if L is not None:
             # dominant-kernel timing: one instrumented step, HIP events around every GEMM launch on the launch stream
             L.PROFILE = []
@@ -1086,6 +1140,8 @@ def main(argv=None):
             res['efficiency_vs_1gpu'] = value / (n_ranks * args.ref_1gpu)
         if multi is not None:
             res['multi_gpu'] = multi
+        if dumped is not None:
+            res['dumped_outputs'] = dumped
         if not dry:
             res['model_tflops'] = VIT_FLOP_PER_IMG[args.workload] * n_ranks * args.batch * args.steps / dt / 1e12
             res['roofline'] = {'bound': 'mfma', 'kernel': ('fp32 (exact-f32 MFMA) GEMM launches of one step (%d: gemm_f32_big_kernel for large M, the 64x64 / skinny kernels elsewhere)' % len(gemm)) if fp32_mode else
@@ -1203,6 +1259,14 @@ def main(argv=None):
                               'batchnorm_class': type(net[1]).__name__}
         print(json.dumps(res), flush=True)
     if dist is not None:
+        # the workload's objects (DDP's reducer, GradReducer, their closures) hold the process group: released first, the group is freed by
+        # destroy_process_group itself.  A gloo group still alive at interpreter exit aborts the rank now and then ("terminate called without
+        # an active exception", signal 6)
+        import gc
+        del step, red
+        for k in ('dry_state', 'reducer', 'sync_group', 'eager_step', 'parity_ctx', 'dump_tree'):
+            args.__dict__.pop(k, None)
+        gc.collect()
         dist.destroy_process_group()
 
 

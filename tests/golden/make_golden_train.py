@@ -8,8 +8,9 @@ modules hand out the per-stage output dicts WITH their autograd graph (the relea
   * every per-stage output, ``global_output`` (whmr.py:630-654: hooks on the global-orientation head and the last SMPL call), the BatchNorm running
     statistics after the step and every parameter gradient -- ``global_orient.*`` included, through the third cotangent
     ``oracle.train.global_cotangent_loss`` -- are asserted equal to the oracle's (functional restatement + torch autograd);
-  * the fixture stores the loss, per-parameter gradient (L2 norm, sum) pairs for all trained parameters, a few small gradients in full
-    and the updated running statistics -- plain arrays only.
+  * the fixture stores the loss, per-parameter gradient (L2 norm, sum) pairs for all trained parameters, a few small gradients in full,
+    the updated running statistics and, for the STAGE 2 runs, the reference's ReLU decisions of the three deconv stages where the pre-activation
+    is within rounding of zero, with the open gates per channel (the oracle pass above runs on the reference's decisions) -- plain arrays only.
 Usage:  python tests/golden/make_golden_train.py
 """
 import importlib.util
@@ -35,6 +36,7 @@ FULL_KEYS = ('dp_head.predict_ann_index.bias', 'regressor.2.deccam.weight', 'reg
              'maf_extractor.2.conv2.bias', 'maf_extractor.0.conv2.weight', 'transformer_decoder.norm1.weight', 'conv.1.weight',
              'feature_extractor.backbone.last_norm.weight', 'feature_extractor.backbone.blocks.0.attn.qkv.bias', 'global_orient.decrot.weight',
              'global_orient.fc2.bias')
+RELU_NEAR = 1e-4
 SKIP = ('running', 'cam_model', 'smpl', 'Dmap', 'points_grid', 'init_', 'num_batches')
 
 
@@ -75,6 +77,12 @@ def main():
     go_cap, smpl_cap = [], []
     net.global_orient.register_forward_hook(lambda m, i, o: go_cap.append((i[1], o)))
     net.regressor[0].smpl.register_forward_hook(lambda m, i, o: smpl_cap.append(o))
+    # the ReLU pre-activations of the three deconv stages (ConvTranspose2d, BatchNorm2d, in-place ReLU: the BatchNorm output, copied before the ReLU
+    # overwrites it).  The reference's decisions go to the oracle, so that the gradients compare on any CPU -- a pre-activation within fp32 rounding of
+    # zero is decided differently by another machine's kernels, and one flipped gate moves the backbone gradients by ~1e-4
+    z_cap = []
+    for j in (1, 4, 7):
+        net.deconv_layers[j].register_forward_hook(lambda m, i, o: z_cap.append(o.detach().clone()))
     from utils.geometry import rotation_matrix_to_angle_axis as ref_mat_to_aa
     fixture = {'grad_keys': np.array(keys)}
 
@@ -107,9 +115,11 @@ def main():
         del dp_cap[:]
         del go_cap[:]
         del smpl_cap[:]
+        del z_cap[:]
         net(inp['x'], None, inp['center'], inp['scale'], inp['bbox_height'], inp['orig_shape'], inp['bbox_info'], is_train=True,
             J_regressor=None, full_x=inp['full_x'])
-        assert len(cap) == 3
+        assert len(cap) == 3 and len(z_cap) == 3
+        gate_cap = [z > 0 for z in z_cap]
         loss_ref = OT.cotangent_loss([None] + cap)
         assert len(dp_cap) == 1                      # AUX_SUPV_ON: the IUV head ran on the last feature map (whmr.py:656-658)
         loss_dp_ref = OT.dp_cotangent_loss(dp_cap[0])
@@ -129,10 +139,12 @@ def main():
         with torch.no_grad():
             cam_rotmat, _ = OW.cam_model_forward(sd, inp['full_x'])          # the oracle's own camera head (pinned by make_golden.py); whmr.py:509-524
         assert rel(cam_rotmat, cam_rotmat_ref) < 2e-5
+        fm = []
         outs = OT.whmr_forward_train(p, MG.ASSETS, inp['x'], inp['center'], inp['scale'], inp['bbox_height'], inp['orig_shape'],
                                      inp['bbox_info'], stage=stage, stats=stats, dp_out=dp,
                                      drop_masks=drop_masks if with_dp else None, drop_path_rate=rate if with_dp else 0.0,
-                                     global_out=gout, cam_rotmat=cam_rotmat_ref)
+                                     global_out=gout, cam_rotmat=cam_rotmat_ref, relu_gates=gate_cap, fmaps_out=fm)
+        assert [tuple(g.shape) for g in gate_cap] == [tuple(f.shape) for f in fm]
         loss = OT.cotangent_loss(outs)
         loss_dp = OT.dp_cotangent_loss(dp[0])
         loss_g = OT.global_cotangent_loss(gout[0])
@@ -176,6 +188,14 @@ def main():
             fixture['grad_%s/%s' % (tag, k)] = ref_named[k].grad.numpy().copy()
         for k in stats:
             fixture['stat_%s/%s' % (tag, k)] = ref_state[k].numpy().copy()
+        if stage == 2:                                # the runs tests/test_oracle_cpu.py replays (STAGE 1 has the same forward, hence the same gates)
+            # only the decisions another CPU could take differently: the positions whose pre-activation is within 1e-4 of the map's RMS of zero
+            # (fp32 rounding moves it by ~1e-6), and the open gates per channel, which pin every other decision
+            for j, (z, g) in enumerate(zip(z_cap, gate_cap)):
+                near = torch.nonzero(z.reshape(-1).abs() < RELU_NEAR * z.pow(2).mean().sqrt()).reshape(-1)
+                fixture['relu_near_%s/%d' % (tag, j)] = near.numpy().astype(np.int32)
+                fixture['relu_near_open_%s/%d' % (tag, j)] = g.reshape(-1)[near].numpy()
+                fixture['relu_open_per_channel_%s/%d' % (tag, j)] = g.sum(dim=(0, 2, 3)).numpy().astype(np.int32)
     np.savez_compressed(os.path.join(HERE, 'whmr_train_b2.npz'), **fixture)
     print('wrote whmr_train_b2.npz')
 

@@ -24,16 +24,31 @@ def test_oracle_whmr_forward_matches_reference_fixture(assets, state_dict):
     from oracle import whmr as OW
     g = np.load(os.path.join(GOLDEN, 'whmr_b2.npz'))
     t = lambda k: torch.from_numpy(g['in_' + k])
+    from oracle import geometry as OG
     taps = {}
     with torch.no_grad():
         out = OW.whmr_forward(state_dict, assets, t('x'), t('center'), t('scale'), t('bbox_height'), t('orig_shape'),
                               t('bbox_info'), full_x=t('full_x'), taps=taps)
+        stages = OW.whmr_forward(state_dict, assets, t('x'), t('center'), t('scale'), t('bbox_height'), t('orig_shape'),
+                                 t('bbox_info'), full_x=t('full_x'), view='train')[0]['smpl_out']
     for k, v in out.items():
         assert _rel(v, g['out_' + k]) < 1e-5, k
     assert _rel(taps['s_feat0'], g['s_feat']) < 1e-5
     assert _rel(taps['Tz'], g['Tz']) < 1e-5
     for i in range(3):
-        assert _rel(taps['ref_feature'][i], g['ref_feature%d' % i]) < 1e-5
+        for name in g.files:
+            if name.startswith('iter%d_' % i):                  # the regressor stage's outputs: they place the next stage's sample points
+                assert _rel(stages[i + 1][name.split('_', 1)[1]], g[name]) < 1e-5, name
+        # the sampled features at the points the reference sampled: the fixed grid, then the previous stage's markers projected with its camera.
+        # Sampled at its own points instead, the oracle moves a feature by up to 1e-5 where the map is steep for a 2e-7 move of a point
+        # (fp32 rounding that differs with the machine's CPU kernels)
+        if i == 0:
+            ref = taps['ref_feature'][0]
+        else:
+            pts = OG.projection(torch.from_numpy(g['iter%d_verts' % (i - 1)])[:, assets['ssm']], torch.from_numpy(g['iter%d_theta' % (i - 1)])[:, :3])
+            with torch.no_grad():
+                ref, _ = OW.maf_sampling(state_dict, pts, taps['fmaps'][i], 'maf_extractor.%d.' % i)
+        assert _rel(ref, g['ref_feature%d' % i]) < 1e-5
         fm = taps['fmaps'][i]
         assert _rel(fm.reshape(-1)[torch.from_numpy(g['fmap%d_idx' % i])], g['fmap%d_val' % i]) < 1e-5
         assert abs(fm.double().sum().item() - g['fmap%d_sum' % i][0]) < 1e-3 * g['fmap%d_sum' % i][1]
@@ -246,10 +261,28 @@ def test_train_oracle_matches_reference_fixture(assets, state_dict, droppath):
     stats, dp, gout = {}, [], []
     tag = 'stage2_droppath' if droppath else 'stage2'
     masks = torch.from_numpy(fx['drop_masks']) if droppath else None
+    # the reference's ReLU decisions of the three deconv stages: a pre-activation within fp32 rounding of zero is decided differently by another
+    # machine's CPU kernels, and one flipped gate moves the backbone gradients by ~1e-4.  The oracle runs on its own decisions (an ungated pass)
+    # with the reference's at the positions the fixture lists as near zero, where the two may differ in a handful of places only; the open gates
+    # per channel then equal the reference's, so no decision elsewhere differs
+    own = []
+    with torch.no_grad():
+        OT.whmr_forward_train(state_dict, assets, inp['x'], inp['center'], inp['scale'], inp['bbox_height'], inp['orig_shape'], inp['bbox_info'],
+                              stage=2, drop_masks=masks, drop_path_rate=0.3 if droppath else 0.0, fmaps_out=own)
+    gates, flips = [], []
+    for j, f in enumerate(own):
+        g_ = (f > 0).reshape(-1)
+        near = torch.from_numpy(fx['relu_near_%s/%d' % (tag, j)].astype(np.int64))
+        ref_open = torch.from_numpy(fx['relu_near_open_%s/%d' % (tag, j)])
+        flips.append(int((g_[near] != ref_open).sum()))
+        g_[near] = ref_open
+        gates.append(g_.view(f.shape))
+        assert torch.equal(gates[j].sum(dim=(0, 2, 3)), torch.from_numpy(fx['relu_open_per_channel_%s/%d' % (tag, j)]).long()), j
+    assert sum(flips) <= 1e-5 * sum(g_.numel() for g_ in gates), flips
     # global_output (whmr.py:630-654) with the camera rotation the reference's cam_model produced for the fixture's full image
     outs = OT.whmr_forward_train(p, assets, inp['x'], inp['center'], inp['scale'], inp['bbox_height'], inp['orig_shape'], inp['bbox_info'],
                                  stage=2, stats=stats, dp_out=dp, drop_masks=masks, drop_path_rate=0.3 if droppath else 0.0,
-                                 global_out=gout, cam_rotmat=torch.from_numpy(fx['cam_rotmat']))
+                                 global_out=gout, cam_rotmat=torch.from_numpy(fx['cam_rotmat']), relu_gates=gates)
     loss, loss_dp, loss_g = OT.cotangent_loss(outs), OT.dp_cotangent_loss(dp[0]), OT.global_cotangent_loss(gout[0])
     (loss + loss_dp + loss_g).backward()
     assert abs(loss.item() - float(fx['loss_' + tag])) < 1e-5 and abs(loss_dp.item() - float(fx['loss_dp_' + tag])) < 1e-5
@@ -260,7 +293,7 @@ def test_train_oracle_matches_reference_fixture(assets, state_dict, droppath):
     ns = fx['grad_norm_sum_' + tag]
     for i, k in enumerate(keys):
         g = p[k].grad.double()
-        if ns[i, 0] < 1e-8:
+        if ns[i, 0] < 1e-7 * ns[:, 0].max():        # a bias in front of a batch-statistics BatchNorm: zero in exact arithmetic, rounding noise in the fixture
             assert g.norm().item() < 1e-6, k
             continue
         assert abs(g.norm().item() - ns[i, 0]) < 2e-4 * ns[i, 0], k
