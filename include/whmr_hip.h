@@ -150,6 +150,31 @@ int whmr_patch_im2col_blk(const float* x, void* cols, int B, int Cin, int H, int
                           void* stream);
 /* whmr_attention (bf16, d = 64, 64 < N <= 256) on blocked qkv [ceil(B*N/32)][3*H*8][32][8] -> blocked out [ceil(B*N/32)][H*8][32][8]. */
 int whmr_attention_blk(const void* qkv, void* out, int B, int N, int H, float scale, void* stream);
+/* ---- MXFP8 pilot of the bf16 ViT inference path (off by default, WHMR_MX_PILOT=1; gemm_blk_mx.hip, mx_common.h): the four Linears of every ViT block (vit.py:66-68,93,96) as block-scaled FP8 GEMMs
+ * on v_mfma_scale_f32_32x32x64_f8f6f4.  Elements OCP e4m3fn (max 448, subnormals kept); 32 consecutive elements along K of one row share an E8M0 scale
+ * byte s (value 2^(s-127)); e = the smallest integer with amax <= 448 * 2^e, clamped to [-127, 127] (all-zero block: -127), q = RNE(x * 2^-e).
+ * MX operand = data [ceil(R/32)][K/16][32][16] bytes (the 512-byte unit of the bf16 layout) + scales [ceil(R/32)][K/128][32][4] bytes (byte j of row r
+ * in group g: block 4 g + j).  K % 128 == 0. */
+struct whmr_gemm_blk_mx_desc {
+    const void* A;        /* e4m3 [ceil(M/32)][K/16][32][16] */
+    const void* A_scale;  /* e8m0 [ceil(M/32)][K/128][32][4] */
+    const void* W;        /* e4m3 [N/32][K/16][32][16] (nn.Linear weight [N, K], quantised once) */
+    const void* W_scale;  /* e8m0 [N/32][K/128][32][4] */
+    void* C;              /* epi 0: bf16 blocked [ceil(M/32)][N/8][32][8]; epi 1: e4m3 [ceil(M/32)][N/16][32][16]; epi 2: fp32 blocked [ceil(M/32)][N/4][32][4] */
+    void* C_scale;        /* epi 1: e8m0 [ceil(M/32)][N/128][32][4] */
+    const float* bias;    /* [N] or null */
+    const float* res;     /* epi 2: fp32 blocked like C (may alias C) */
+    int32_t M, N, K;      /* N % 128 == 0, K % 128 == 0; buffers hold whole 32-row blocks */
+    int32_t epi;          /* 0: bf16(acc + bias) (qkv); 1: MX(gelu(acc + bias)) (fc1, the GELU of the bf16 path); 2: fp32(acc + bias + res) (proj, fc2) */
+    int32_t tile;         /* 0 = chooser; 0x42 = 256 x 128, 0x22 = 128 x 128 */
+    int32_t reserved;     /* 0 */
+};
+int whmr_gemm_blk_mx(const struct whmr_gemm_blk_mx_desc* p, void* stream);
+/* src [R, K] -> MX operand (data q, scales s as above; rows R .. ceil(R/32)*32 - 1 written as zeros).  kind 0: fp32 row-major, 1: bf16 row-major,
+ * 2: bf16 blocked [ceil(R/32)][K/8][32][8] (the blocked attention's output, as proj's operand). */
+int whmr_quantize_mx(const void* src, int kind, void* q, void* s, int R, int K, void* stream);
+/* LayerNorm (vit.py:125,133) of the blocked fp32 stream -> MX operand (same statistics as whmr_layernorm_blk; C in {256, 768, 1024, 1280}). */
+int whmr_layernorm_blk_mx(const float* x, const float* gamma, const float* beta, void* y_data, void* y_scale, int rows, int C, float eps, void* stream);
 /* bf16x3 numerics for the row-major / convolution GEMMs (whmr.py:419,488-498): fp32 rows [rows, C] -> bf16 rows [rows, 3C] = [hi | lo | hi]; with the
  * weights laid out [W_hi | W_hi | W_lo] along the same (per-tap channel) axis ONE whmr_gemm_bf16 launch with Cin' = 3 Cin accumulates the three
  * split products in fp32. */

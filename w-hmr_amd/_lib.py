@@ -38,6 +38,13 @@ class WhmrGemmBlk(C.Structure):
                 ('shift', C.c_void_p), ('shift_stats', C.c_void_p), ('shift_out', C.c_void_p), ('xhat_lo', C.c_void_p)]
 
 
+class WhmrGemmBlkMx(C.Structure):
+    """struct whmr_gemm_blk_mx_desc (include/whmr_hip.h): MXFP8 GEMM of the MX pilot of the ViT inference path"""
+    _fields_ = [('A', C.c_void_p), ('A_scale', C.c_void_p), ('W', C.c_void_p), ('W_scale', C.c_void_p), ('C', C.c_void_p), ('C_scale', C.c_void_p),
+                ('bias', C.c_void_p), ('res', C.c_void_p),
+                ('M', C.c_int32), ('N', C.c_int32), ('K', C.c_int32), ('epi', C.c_int32), ('tile', C.c_int32), ('reserved', C.c_int32)]
+
+
 class WhmrSmplModel(C.Structure):
     _fields_ = [('v_template', C.c_void_p), ('shapedirs', C.c_void_p), ('posedirs', C.c_void_p),
                 ('lbs_weights', C.c_void_p), ('J_template', C.c_void_p), ('J_shapedirs', C.c_void_p),
@@ -88,6 +95,9 @@ _SIGS = {
     'whmr_gemm_blk_set_tile': [_I, _I],
     'whmr_gemm_blk_chain': [C.POINTER(WhmrGemmBlk), C.POINTER(WhmrGemmBlk), _P, _P, _P],
     'whmr_layernorm_blk': [_P, _P, _P, _P, _I, _I, _F, _I, _P],
+    'whmr_gemm_blk_mx': [C.POINTER(WhmrGemmBlkMx), _P],
+    'whmr_quantize_mx': [_P, _I, _P, _P, _I, _I, _P],
+    'whmr_layernorm_blk_mx': [_P, _P, _P, _P, _P, _I, _I, _F, _P],
     'whmr_patch_im2col_blk': [_P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P],
     'whmr_attention_blk': [_P, _P, _I, _I, _I, _F, _P],
     'whmr_split3_bf16': [_P, _P, _L, _I, _P],
@@ -513,6 +523,89 @@ def _blk_desc(a, w, out, M, bias=None, epi=EPI_BF16, res=None, res_rows=0, tile=
             p.C_lo = out_lo.data_ptr()
     p._keep = (a, w, out, bias, res, xhat, stats_out, stats_in, colsum, a_lo, w_lo, out_lo, shift, shift_stats, shift_out, xhat_lo)
     return p, x3, N, K
+
+
+# ---- MX operands of the MX pilot (csrc/mx_common.h): e4m3 data [ceil(R/32)][K/16][32][16] + e8m0 scales [ceil(R/32)][K/128][32][4], uint8 tensors
+MX_EPI_BF16, MX_EPI_GELU_MX, MX_EPI_F32_RES = 0, 1, 2
+
+
+def mx_empty(R, K, device):
+    """(data, scales) uint8 buffers of an MX operand of R rows (padded to 32) and K columns (K % 128 == 0)"""
+    assert K % 128 == 0
+    nb = (R + 31) // 32
+    return (torch.empty((nb, K // 16, 32, 16), dtype=torch.uint8, device=device), torch.empty((nb, K // 128, 32, 4), dtype=torch.uint8, device=device))
+
+
+def quantize_mx(src, out=None, rows=None):
+    """-> (data, scales): src fp32 / bf16 row-major [R, K], or a blocked bf16 [ceil(R/32)][K/8][32][8] tensor with ``rows`` = R, quantised to the MX
+    operand (scale rule and rounding: include/whmr_hip.h).  ``out``: a (data, scales) pair to write into (the forward's workspace)."""
+    _dev(src)
+    assert src.is_contiguous()
+    if src.dim() == 4:
+        assert src.dtype == torch.bfloat16 and src.shape[2:] == (32, 8) and rows is not None and src.shape[0] * 32 >= rows
+        kind, R, K = 2, rows, src.shape[1] * 8
+    else:
+        assert src.dim() == 2 and src.dtype in (torch.float32, torch.bfloat16)
+        kind, (R, K) = (0 if src.dtype == torch.float32 else 1), src.shape
+    q, s = out if out is not None else mx_empty(R, K, src.device)
+    assert q.dtype == torch.uint8 and s.dtype == torch.uint8 and q.shape == ((R + 31) // 32, K // 16, 32, 16) and s.shape == ((R + 31) // 32, K // 128, 32, 4)
+    ev = _profile_begin()
+    _check(lib().whmr_quantize_mx(src.data_ptr(), kind, q.data_ptr(), s.data_ptr(), R, K, _stream()), 'whmr_quantize_mx')
+    _profile_end(ev, 'quantize_mx_bytes', float(R) * K * (src.element_size() + 1))
+    return q, s
+
+
+def gemm_blk_mx(a, w, out, M, bias=None, epi=MX_EPI_BF16, res=None, out_scale=None, tile=0):
+    """out = epi(deq(a) . deq(w)^T + bias [+ res]) on MX operands a = (data, scales) of M rows and w = (data, scales) of the weight [N, K]:
+    out bf16 blocked [M/32][N/8][32][8] (epi 0), MX data [M/32][N/16][32][16] with ``out_scale`` (epi 1: GELU, then quantised), or fp32 blocked
+    [M/32][N/4][32][4] (epi 2: + blocked ``res``, which may be ``out``)."""
+    (aq, as_), (wq, ws) = a, w
+    _dev(aq, as_, wq, ws, out, bias, res, out_scale)
+    for t in (aq, as_, wq, ws, out):
+        assert t.is_contiguous()
+    assert aq.dtype == torch.uint8 and wq.dtype == torch.uint8 and as_.dtype == torch.uint8 and ws.dtype == torch.uint8
+    N, K = wq.shape[0] * 32, wq.shape[1] * 16
+    assert aq.shape[1] * 16 == K and aq.shape[0] * 32 >= M and out.shape[0] * 32 >= M and as_.shape[:2] == (aq.shape[0], K // 128)
+    assert ws.shape[:2] == (wq.shape[0], K // 128)
+    p = WhmrGemmBlkMx()
+    p.A, p.A_scale, p.W, p.W_scale, p.C = aq.data_ptr(), as_.data_ptr(), wq.data_ptr(), ws.data_ptr(), out.data_ptr()
+    if epi == MX_EPI_BF16:
+        assert out.dtype == torch.bfloat16 and out.shape[1] * 8 == N
+    elif epi == MX_EPI_GELU_MX:
+        assert out.dtype == torch.uint8 and out.shape[1] * 16 == N and out_scale is not None and out_scale.dtype == torch.uint8
+        assert out_scale.is_contiguous() and out_scale.shape == (out.shape[0], N // 128, 32, 4)
+        p.C_scale = out_scale.data_ptr()
+    else:
+        assert epi == MX_EPI_F32_RES and out.dtype == torch.float32 and out.shape[1] * 4 == N and res is not None
+        assert res.dtype == torch.float32 and res.is_contiguous() and res.shape == out.shape
+        p.res = res.data_ptr()
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
+        p.bias = bias.data_ptr()
+    p.M, p.N, p.K, p.epi, p.tile = M, N, K, epi, tile
+    if PROFILE is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _check(lib().whmr_gemm_blk_mx(C.byref(p), _stream()), 'whmr_gemm_blk_mx')
+        e1.record()
+        PROFILE.append(('gemm_mxfp8', 2.0 * M * N * K, e0, e1))
+        return out
+    _check(lib().whmr_gemm_blk_mx(C.byref(p), _stream()), 'whmr_gemm_blk_mx')
+    return out
+
+
+def layernorm_blk_mx(x, weight, bias, out, rows, eps):
+    """LayerNorm of a blocked fp32 stream [rows/32][C/4][32][4] -> MX operand out = (data, scales) (padded rows written as zeros)"""
+    q, s = out
+    _dev(x, weight, bias, q, s)
+    assert x.dtype == torch.float32 and x.is_contiguous() and q.is_contiguous() and s.is_contiguous()
+    Cdim = x.shape[1] * 4
+    assert q.dtype == torch.uint8 and s.dtype == torch.uint8 and q.shape == (x.shape[0], Cdim // 16, 32, 16) and s.shape == (x.shape[0], Cdim // 128, 32, 4)
+    ev = _profile_begin()
+    _check(lib().whmr_layernorm_blk_mx(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), q.data_ptr(), s.data_ptr(), rows, Cdim, eps, _stream()),
+           'whmr_layernorm_blk_mx')
+    _profile_end(ev, 'layernorm_mx_bytes', float(rows) * Cdim * 5)                  # fp32 stream read once, one byte per element written
+    return out
 
 
 def layernorm_blk(x, weight, bias, out, rows, eps, out_std=False, mean_out=None):

@@ -2,6 +2,7 @@
 //   whmr_layernorm   <- nn.LayerNorm(eps=1e-6) at vit.py:125,133,212,242 (and eps=1e-5 inside the timm Block, whmr.py:423)
 //   whmr_patch_im2col <- the gather half of PatchEmbed's Conv2d(k16, s16, pad 2) at vit.py:157,161 (GEMM half: gemm_*.hip)
 #include "common.h"
+#include "mx_common.h"
 
 // One wave per row; the row is held in registers (C <= 64*4*MAXV), two-pass mean / variance in fp32 like ATen's CPU kernel.
 template <typename TOUT, int MAXV>
@@ -340,6 +341,94 @@ extern "C" int whmr_layernorm_blk_x3(const float* x, const float* gamma, const f
         case 1024: return launch_ln_blk<16, 16>(x, gamma, beta, y_hi, rows, C, eps, 0, st, y_lo, mean_out);
         case 1280: return launch_ln_blk<20, 16>(x, gamma, beta, y_hi, rows, C, eps, 0, st, y_lo, mean_out);
         case 256: return launch_ln_blk<8, 8>(x, gamma, beta, y_hi, rows, C, eps, 0, st, y_lo, mean_out);
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+// Same LayerNorm (same statistics and arithmetic as layernorm_blk_kernel) with the result as the MX operand of the MX pilot (mx_common.h):
+// e4m3 data [rows/32][C/16][32][16] + e8m0 scales [rows/32][C/128][32][4].  NPER is a multiple of 8, so a thread owns whole 32-column blocks of its
+// row and each block's scale is thread-local.  Rows past `rows` in the last block are written as zeros.
+template <int NPER, int PARTS>
+__global__ __launch_bounds__(32 * PARTS) void layernorm_blk_mx_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
+                                                                      uint8_t* __restrict__ yq, uint8_t* __restrict__ ys, int rows, int C, float eps) {
+    static_assert(NPER % 8 == 0, "whole MX blocks per thread");
+    __shared__ float red[2][PARTS][32];
+    const int row = threadIdx.x & 31, part = threadIdx.x >> 5;
+    const int rb = blockIdx.x;
+    const int n4_0 = part * NPER, NC4 = C >> 2;
+    const float* xb = x + ((size_t)rb * NC4 + n4_0) * 128 + row * 4;
+    float4 v[NPER];
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < NPER; ++q) {
+        v[q] = *(const float4*)(xb + q * 128);
+        s += (v[q].x + v[q].y) + (v[q].z + v[q].w);
+    }
+    red[0][part][row] = s;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int pp = 0; pp < PARTS; ++pp) tot += red[0][pp][row];
+    const float mean = tot / (float)C;
+    float qs = 0.f;
+#pragma unroll
+    for (int q = 0; q < NPER; ++q) {
+        const float dx = v[q].x - mean, dy = v[q].y - mean, dz = v[q].z - mean, dw = v[q].w - mean;
+        qs += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    }
+    red[1][part][row] = qs;
+    __syncthreads();
+    float var = 0.f;
+#pragma unroll
+    for (int pp = 0; pp < PARTS; ++pp) var += red[1][pp][row];
+    const float rstd = 1.0f / sqrtf(var / (float)C + eps);
+    const bool live = rb * 32 + row < rows;
+#pragma unroll
+    for (int kb = 0; kb < NPER / 8; ++kb) {
+        float y[32];
+        float amax = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int u = n4_0 + kb * 8 + q;
+            const float4 gg = *(const float4*)(g + u * 4), bb = *(const float4*)(b + u * 4);
+            const float4 w = v[kb * 8 + q];
+            y[4 * q] = live ? (w.x - mean) * rstd * gg.x + bb.x : 0.f;
+            y[4 * q + 1] = live ? (w.y - mean) * rstd * gg.y + bb.y : 0.f;
+            y[4 * q + 2] = live ? (w.z - mean) * rstd * gg.z + bb.z : 0.f;
+            y[4 * q + 3] = live ? (w.w - mean) * rstd * gg.w + bb.w : 0.f;
+            amax = fmaxf(amax, fmaxf(fmaxf(fabsf(y[4 * q]), fabsf(y[4 * q + 1])), fmaxf(fabsf(y[4 * q + 2]), fabsf(y[4 * q + 3]))));
+        }
+        const int ex = mx_scale_exp(amax);
+        const float inv = mx_inv_scale(ex);
+        const int blk = (n4_0 >> 3) + kb;                                // 32-column block of the row
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const float* t = y + 16 * c;
+            *(uint4*)(yq + (((size_t)rb * (C >> 4) + blk * 2 + c) * 32 + row) * 16) =
+                make_uint4(mx_pack4(t[0] * inv, t[1] * inv, t[2] * inv, t[3] * inv), mx_pack4(t[4] * inv, t[5] * inv, t[6] * inv, t[7] * inv),
+                           mx_pack4(t[8] * inv, t[9] * inv, t[10] * inv, t[11] * inv), mx_pack4(t[12] * inv, t[13] * inv, t[14] * inv, t[15] * inv));
+        }
+        ys[(((size_t)rb * (C >> 7) + (blk >> 2)) * 32 + row) * 4 + (blk & 3)] = (uint8_t)(ex + 127);
+    }
+}
+
+template <int NPER, int PARTS>
+static int launch_ln_blk_mx(const float* x, const float* g, const float* b, void* yq, void* ys, int rows, int C, float eps, hipStream_t st) {
+    hipLaunchKernelGGL((layernorm_blk_mx_kernel<NPER, PARTS>), dim3((rows + 31) / 32), dim3(32 * PARTS), 0, st, x, g, b, (uint8_t*)yq, (uint8_t*)ys, rows, C,
+                       eps);
+    WHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int whmr_layernorm_blk_mx(const float* x, const float* gamma, const float* beta, void* y_data, void* y_scale, int rows, int C, float eps,
+                                     void* stream) {
+    if (rows <= 0 || !y_data || !y_scale) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    switch (C) {
+        case 768: return launch_ln_blk_mx<24, 8>(x, gamma, beta, y_data, y_scale, rows, C, eps, st);       // ViT-B
+        case 1024: return launch_ln_blk_mx<16, 16>(x, gamma, beta, y_data, y_scale, rows, C, eps, st);     // ViT-L
+        case 1280: return launch_ln_blk_mx<40, 8>(x, gamma, beta, y_data, y_scale, rows, C, eps, st);      // ViT-H
+        case 256: return launch_ln_blk_mx<8, 8>(x, gamma, beta, y_data, y_scale, rows, C, eps, st);
     }
     return (int)hipErrorInvalidValue;
 }

@@ -102,6 +102,9 @@ class ViT(nn.Module):
         self._ws = {}
         self.blocked = True                 # bf16 inference on the blocked-layout kernels when the shapes allow it
         self.chain_mlp = os.environ.get('WHMR_BLK_CHAIN', '0') != '0'      # pilot: fc1 -> fc2 as one persistent launch (whmr_gemm_blk_chain)
+        # pilot, off by default: the four Linears of every block as MXFP8 GEMMs (_forward_tokens_mx) in the bf16 inference path.  NOT a numerics mode:
+        # measured slower than bf16 and ~13x its error (profiles/r07_mxfp8_first_measurement.txt); kept to measure the FP8 kernels in the model
+        self.mx_pilot = os.environ.get('WHMR_MX_PILOT', '0') != '0'
         self.blocked_min_tokens = 2048      # ... and the batch has at least this many tokens (set 0 to force the blocked path)
         self.x3_min_tokens = 320            # bf16x3: below this many tokens (one 224^2 / 256x192 crop) the exact-f32 path is the faster parity-grade one
         self.ln_fold = True                 # ... with norm1 / norm2 folded into the qkv / fc1 GEMMs (no LayerNorm pass inside the blocks)
@@ -197,6 +200,8 @@ class ViT(nn.Module):
         # (ViT-B 256x192 under a HIP graph, tools/smallbatch_probe.py: batch 1 0.85 vs 1.14 ms, batch 8 1.15 vs 1.22, batch 16 1.50 vs 1.32)
         if (self.blocked and M >= self.blocked_min_tokens and self.numerics == 'bf16' and D % 256 == 0 and hid_dim % 256 == 0 and D // self.num_heads == 64
                 and 64 < N <= 256 and P % 8 == 0 and (Cin * P * P) % 32 == 0 and D in (256, 768, 1024, 1280)):
+            if self.mx_pilot and self.depth:
+                return self._forward_tokens_mx(x, B, Hp, Wp), (B, Hp, Wp)
             return self._forward_tokens_blocked(x, B, Hp, Wp), (B, Hp, Wp)
         cols = self._buf('cols', (M, Cin * P * P), dt, dev)
         L.patch_im2col(x.float(), cols, P, pad)
@@ -294,6 +299,49 @@ class ViT(nn.Module):
             L.layernorm_blk(t, blk.norm2.weight, blk.norm2.bias, h, M, 1e-6)
             L.gemm_blk(h, self._wblk(blk.mlp.fc1.weight), hid, M, bias=blk.mlp.fc1.bias, epi=L.EPI_BF16_GELU)
             L.gemm_blk(hid, self._wblk(blk.mlp.fc2.weight), t, M, bias=blk.mlp.fc2.bias, epi=L.EPI_F32_RES, res=t)
+        out = torch.empty((M, D), dtype=f32, device=dev)
+        L.layernorm_blk(t, self.last_norm.weight, self.last_norm.bias, out, M, 1e-6, out_std=True)
+        return out
+
+    def _wmx(self, p):
+        """MX operand (e4m3 data, e8m0 scales) of a Linear weight [N, K], quantised on the device (re-made when the parameter changes)"""
+        key = ('mx', id(p))
+        ent = self._wcache.get(key)
+        if ent is None or ent[0] != p._version or ent[1][0].device != p.device:
+            ent = (p._version, L.quantize_mx(p.detach().float().contiguous()))
+            self._wcache[key] = ent
+        return ent[1]
+
+    def _forward_tokens_mx(self, x, B, Hp, Wp):
+        """PILOT (``mx_pilot``, bf16 numerics, blocked envelope): the unfolded blocked pipeline with qkv / proj / fc1 / fc2 as MXFP8 GEMMs (e4m3
+        operands with one E8M0 scale per 32 elements along K, fp32 accumulate).  The patch embed GEMM, the attention core, the fp32 residual stream, the LayerNorm statistics and last_norm
+        keep the arithmetic of the 'bf16' path; LayerNorm writes the MX operand directly, fc1 writes GELU's result as fc2's MX operand, and the bf16
+        attention output is quantised by one pass per block."""
+        Cin, P, pad, D, heads = x.shape[1], self.patch_size, self.patch_pad, self.embed_dim, self.num_heads
+        N, M = Hp * Wp, B * Hp * Wp
+        nb = (M + 31) // 32
+        dev, bf, f32, u8 = x.device, torch.bfloat16, torch.float32, torch.uint8
+        K0 = Cin * P * P
+        hd = self.blocks[0].mlp.fc1.weight.shape[0]
+        cols = self._buf('cols_blk', (nb, K0 // 8, 32, 8), bf, dev)
+        L.patch_im2col_blk(x.float(), cols, P, pad)
+        pos = self._pos(N, D, dev)                                                    # vit.py:320
+        t = self._buf('t_blk', (nb, D // 4, 32, 4), f32, dev)
+        L.gemm_blk(cols, self._wblk(self.patch_embed.proj.weight, (D, K0)), t, M, bias=self.patch_embed.proj.bias, epi=L.EPI_F32_POS,
+                   res=pos, res_rows=N)
+        mx = lambda name, cols_: (self._buf(name + '_q', (nb, cols_ // 16, 32, 16), u8, dev), self._buf(name + '_s', (nb, cols_ // 128, 32, 4), u8, dev))
+        h, atq, hid = mx('mx_h', D), mx('mx_att', D), mx('mx_hid', hd)
+        qkv = self._buf('qkv_blk', (nb, 3 * D // 8, 32, 8), bf, dev)
+        att = self._buf('att_blk', (nb, D // 8, 32, 8), bf, dev)
+        for blk in self.blocks:
+            L.layernorm_blk_mx(t, blk.norm1.weight, blk.norm1.bias, h, M, 1e-6)
+            L.gemm_blk_mx(h, self._wmx(blk.attn.qkv.weight), qkv, M, bias=blk.attn.qkv.bias, epi=L.MX_EPI_BF16)
+            L.attention_blk(qkv, att, B, N, heads, self.scale)
+            L.quantize_mx(att, out=atq, rows=M)
+            L.gemm_blk_mx(atq, self._wmx(blk.attn.proj.weight), t, M, bias=blk.attn.proj.bias, epi=L.MX_EPI_F32_RES, res=t)
+            L.layernorm_blk_mx(t, blk.norm2.weight, blk.norm2.bias, h, M, 1e-6)
+            L.gemm_blk_mx(h, self._wmx(blk.mlp.fc1.weight), hid[0], M, bias=blk.mlp.fc1.bias, epi=L.MX_EPI_GELU_MX, out_scale=hid[1])
+            L.gemm_blk_mx(hid, self._wmx(blk.mlp.fc2.weight), t, M, bias=blk.mlp.fc2.bias, epi=L.MX_EPI_F32_RES, res=t)
         out = torch.empty((M, D), dtype=f32, device=dev)
         L.layernorm_blk(t, self.last_norm.weight, self.last_norm.bias, out, M, 1e-6, out_std=True)
         return out
