@@ -1,9 +1,12 @@
 """Benchmark of the W-HMR hot path on MI355X.  Contract: see the task brief / DESIGN.md "Measurement".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload vit224|vit256x192|vitl256x192|whmr|whmr_train] [--no-cpu] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload vit224|vit256x192|vitl256x192|whmr|whmr_train] [--dump-outputs DIR] [--full [--no-cpu] ...]
 
 A step = one forward of the hot path over one batch of 64 synthetic crops per GPU (inputs resident in HBM).
 N=1 default workload = BASELINE.json configs[1]: ViT-B/16 backbone only, 224x224, batch 64, bf16 MFMA.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line: nothing else.  `--full` adds what runs after the
+timed region: the instrumented step (roofline), the clock probe and the MFMA / HBM ceilings, CPU baselines, parity against the CPU oracle, the
+whmr HBM rows and fp32 leg, and the default run's secondary legs; --no-cpu / --no-parity / --no-ceilings / --no-secondary trim a --full run.
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process is only a LAUNCHER -- it never touches the GPU, starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py ...` as a CHILD process (never an
 exec), relays rank 0's JSON line and exits with the child's return code.  Under torch.distributed.run (WORLD_SIZE set) it is one rank
@@ -44,8 +47,11 @@ def parse(argv=None):
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--workload', default='vit224')
     ap.add_argument('--numerics', default='bf16')
-    ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline leg')
-    ap.add_argument('--no-parity', action='store_true', help='whmr: skip the parity / fp32-mode leg (rocprofv3 runs: keeps the kernel table to the timed path)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also measure what the headline does not need: roofline (instrumented step), clock and ceilings, CPU '
+                         'baseline, parity, whmr HBM rows / fp32 leg, secondary legs (the --no-* options below trim these)')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the CPU baseline leg')
+    ap.add_argument('--no-parity', action='store_true', help='--full, whmr: skip the parity / fp32-mode leg (rocprofv3 runs: keeps the kernel table to the timed path)')
     ap.add_argument('--graph', action='store_true', help='whmr_train on one GPU: replay the whole step from one HIP graph')
     ap.add_argument('--loss', default='multi-tensor', choices=['multi-tensor', 'per-tensor'],
                     help='whmr_train: the synthetic L2 loss over the 27 supervised tensors as one concatenated weighted dot product (default: 4 launches) or as '
@@ -67,9 +73,9 @@ def parse(argv=None):
                          'DistributedDataParallel(model, device_ids=[gpu], find_unused_parameters=True); needs a process group (torch.distributed.run)')
     ap.add_argument('--always-bucket', action='store_true',
                     help='whmr_train: pack and exchange the gradient buckets even at world size 1 (one-rank RCCL smoke of the reducer on a 1-GPU box)')
-    ap.add_argument('--no-ceilings', action='store_true', help='skip the attainable-ceiling / clock-probe kernels (rocprofv3 runs: keeps them out of the kernel table)')
+    ap.add_argument('--no-ceilings', action='store_true', help='--full: skip the attainable-ceiling / clock-probe kernels (rocprofv3 runs: keeps them out of the kernel table)')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='default run (vit224, 1 GPU): skip the short secondary legs (the same workload in bf16x3, BASELINE configs[2] whmr, configs[3] whmr_train)')
+                    help='--full, default workload (vit224, 1 GPU): skip the short secondary legs (the same workload in bf16x3, BASELINE configs[2] whmr, configs[3] whmr_train)')
     ap.add_argument('--rank-timeout', type=float, default=1500.0,
                     help='launcher: seconds after which the child ranks are killed (process group) and the launcher exits 124; also the collective timeout')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -1083,7 +1089,7 @@ def main(argv=None):
         if args.dump_outputs and rank == 0:          # before the instrumented step below rewrites graph outputs and gradients
             dumped = dump_outputs(getattr(args, 'dump_tree', lambda out: out)(last), args.dump_outputs)
         del last
-        if L is not None:
+        if L is not None and args.full:
             # dominant-kernel timing: one instrumented step, HIP events around every GEMM launch on the launch stream
             L.PROFILE = []
             getattr(args, 'eager_step', step)()
@@ -1104,7 +1110,7 @@ def main(argv=None):
     x3_mode = args.numerics == 'bf16x3'                               # parity-grade numerics on the bf16 pipes: three bf16 MFMAs per product
     gemm_name = 'gemm_f32' if fp32_mode else ('gemm_bf16x3' if x3_mode else 'gemm_bf16')
     gemm = [(f, e0.elapsed_time(e1) * 1e-3) for (name, f, e0, e1) in prof if name == gemm_name]
-    traffic = gemm_traffic() if (args.workload == 'vit224' and not dry and args.numerics == 'bf16') else None        # the PMC passes measured the bf16 kernels
+    traffic = gemm_traffic() if (args.full and args.workload == 'vit224' and not dry and args.numerics == 'bf16') else None    # the PMC passes measured the bf16 kernels
     n_launch = max(len(gemm), 1)
     flops_per_launch = sum(f for f, _ in gemm) / n_launch
     avg_s = sum(t for _, t in gemm) / n_launch
@@ -1144,6 +1150,7 @@ def main(argv=None):
             res['dumped_outputs'] = dumped
         if not dry:
             res['model_tflops'] = VIT_FLOP_PER_IMG[args.workload] * n_ranks * args.batch * args.steps / dt / 1e12
+        if not dry and args.full:
             res['roofline'] = {'bound': 'mfma', 'kernel': ('fp32 (exact-f32 MFMA) GEMM launches of one step (%d: gemm_f32_big_kernel for large M, the 64x64 / skinny kernels elsewhere)' % len(gemm)) if fp32_mode else
                                ('split-bf16 (bf16x3) GEMM launches of one step (%d: gemm_blk_kernel<X3>; achieved / frac count the ALGORITHMIC 2MNK flops -- the '
                                 'matrix pipes issue three bf16 MFMAs per product, see mfma_issue_frac)' % len(gemm)) if x3_mode else
@@ -1248,7 +1255,7 @@ def main(argv=None):
                 except Exception as e:                  # noqa: BLE001
                     import traceback
                     res['secondary'] = {'error': '%s: %s' % (type(e).__name__, e), 'where': traceback.format_exc().strip().splitlines()[-3:]}
-        else:
+        if dry:
             st = getattr(args, 'dry_state', None)
             if st is not None:
                 net, unused, red = st

@@ -335,6 +335,19 @@ def test_bench_entry_launches_its_own_ranks_gloo():
     assert one['n_gpus'] == 1 and one['config']['global_batch'] == 16
 
 
+def test_bench_full_is_opt_in():
+    """a plain run times the steps and prints its line; `--full` (roofline, ceilings, CPU baseline, parity, secondary legs) is off by default,
+    and a run with it prints the same headline fields"""
+    import bench
+    assert not bench.parse([]).full and bench.parse(['--full', '--no-cpu']).full
+    plain = _run_bench('--gpus', '1', '--steps', '2', '--warmup', '0')
+    full = _run_bench('--gpus', '1', '--steps', '2', '--warmup', '0', '--full')
+    for line in (plain, full):
+        assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'} <= set(line)
+        assert abs(line['value'] - 16 * 2 / (line['ms_per_step'] * 2e-3)) < 1e-6 * line['value']
+    assert (plain['metric'], plain['unit'], plain['dtype']) == (full['metric'], full['unit'], full['dtype'])
+
+
 def test_bench_train_entry_two_ranks_gloo():
     """`bench.py --workload whmr_train --gpus 2` drives GradReducer (with a never-used parameter, as global_orient.* in W-HMR: the reference
     needs DDP's find_unused_parameters, core/trainer.py:84-91) and broadcast_buffers through the real entry point; the averaged gradient

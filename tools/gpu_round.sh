@@ -21,7 +21,7 @@ python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1 
 grep "smoke ok" $OUT/${TAG}_smoke.log
 bench() {  # name, args...
   local n=$1; shift
-  python bench.py "$@" > $PROF/${TAG}_bench_$n.json 2> $OUT/${TAG}_bench_$n.err || fail "bench $n failed: $(tail -2 $OUT/${TAG}_bench_$n.err)"
+  python bench.py --full "$@" > $PROF/${TAG}_bench_$n.json 2> $OUT/${TAG}_bench_$n.err || fail "bench $n failed: $(tail -2 $OUT/${TAG}_bench_$n.err)"
   [ -s $PROF/${TAG}_bench_$n.json ] || fail "bench $n wrote nothing"
   grep '^{' $PROF/${TAG}_bench_$n.json | tail -1 > $PROF/${TAG}_bench_$n.json.tmp && mv $PROF/${TAG}_bench_$n.json.tmp $PROF/${TAG}_bench_$n.json    # (RCCL prints a banner to stdout)
   [ -s $PROF/${TAG}_bench_$n.json ] || fail "bench $n printed no JSON line"
@@ -43,10 +43,10 @@ bench whmr_b1 --workload whmr --batch 1 --no-cpu --no-parity --steps 50 --warmup
 cd /tmp
 prof() {  # name, description, bench args...
   local n=$1 d=$2; shift 2
-  rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof_$n -o $n -- python3 $R/bench.py --no-ceilings "$@" > $OUT/${TAG}_prof_$n.log 2>&1
+  rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof_$n -o $n -- python3 $R/bench.py --full --no-ceilings "$@" > $OUT/${TAG}_prof_$n.log 2>&1
   local db=$(find $OUT/${TAG}_prof_$n -name '*.db' | head -1)
   [ -n "$db" ] || fail "no rocprof database for $n"
-  { hdr "rocprofv3 --kernel-trace --stats -- python3 bench.py $*   ($d)"; python3 $R/tools/rocprof_summary.py $db | tail -n +2; } > $PROF/${TAG}_${n}_kernel_stats.txt
+  { hdr "rocprofv3 --kernel-trace --stats -- python3 bench.py --full $*   ($d)"; python3 $R/tools/rocprof_summary.py $db | tail -n +2; } > $PROF/${TAG}_${n}_kernel_stats.txt
   rm -rf $OUT/${TAG}_prof_$n
 }
 prof vit224_b64 "ViT-B/16 224^2 batch 64 bf16: timed steps + warm-ups + 1 instrumented step in the trace" --no-cpu --no-secondary --steps 10 --warmup 3
@@ -55,14 +55,14 @@ prof whmr_b64 "full W-HMR forward, batch 64 + one 600x800 frame, bf16, HIP-graph
 prof whmr_b64_serial "the same forward with the side streams folded into the main one (eager): every kernel's duration WITHOUT concurrency" --workload whmr --serial --no-cpu --no-parity --steps 10 --warmup 3
 prof whmr_train_b64 "W-HMR training step, batch 64, bf16, Adam inside the step" --workload whmr_train --no-cpu --steps 4 --warmup 2
 # timeline of one replayed full forward (every launch with start offset / duration / HSA queue)
-rocprofv3 --kernel-trace -d $OUT/${TAG}_prof_tl -o tl -- python3 $R/bench.py --no-ceilings --workload whmr --no-cpu --no-parity --steps 10 --warmup 3 > $OUT/${TAG}_prof_tl.log 2>&1
+rocprofv3 --kernel-trace -d $OUT/${TAG}_prof_tl -o tl -- python3 $R/bench.py --full --no-ceilings --workload whmr --no-cpu --no-parity --steps 10 --warmup 3 > $OUT/${TAG}_prof_tl.log 2>&1
 TDB=$(find $OUT/${TAG}_prof_tl -name '*.db' | head -1)
 [ -n "$TDB" ] || fail "no rocprof database for the timeline"
-{ hdr "rocprofv3 --kernel-trace -- python3 bench.py --workload whmr --no-cpu --no-parity --steps 10 --warmup 3 ; python3 tools/whmr_timeline.py <db>   (the profiler serialises queues and stretches small launches)"; python3 $R/tools/whmr_timeline.py $TDB 0; } > $PROF/${TAG}_whmr_timeline.txt
+{ hdr "rocprofv3 --kernel-trace -- python3 bench.py --full --workload whmr --no-cpu --no-parity --steps 10 --warmup 3 ; python3 tools/whmr_timeline.py <db>   (the profiler serialises queues and stretches small launches)"; python3 $R/tools/whmr_timeline.py $TDB 0; } > $PROF/${TAG}_whmr_timeline.txt
 rm -rf $OUT/${TAG}_prof_tl
 pmc() {  # name, counters (quoted), bench args...
   local n=$1 c=$2; shift 2
-  rocprofv3 --kernel-trace --pmc $c -d $OUT/${TAG}_pmc_$n -o pmc -- python3 $R/bench.py --no-ceilings "$@" > $OUT/${TAG}_pmc_$n.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c -d $OUT/${TAG}_pmc_$n -o pmc -- python3 $R/bench.py --full --no-ceilings "$@" > $OUT/${TAG}_pmc_$n.log 2>&1
   local db=$(find $OUT/${TAG}_pmc_$n -name '*.db' | head -1)
   [ -n "$db" ] || fail "no PMC database for $n"
   echo $db
@@ -75,12 +75,12 @@ WF=$(pmc whmr_FETCH FETCH_SIZE --workload whmr --eager --no-cpu --no-parity --st
 WW=$(pmc whmr_WRITE WRITE_SIZE --workload whmr --eager --no-cpu --no-parity --steps 3 --warmup 2)
 cd $R
 K="gemm_blk|attention|layernorm|patch"
-{ hdr "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -- python3 bench.py --no-cpu --no-secondary --steps 3 --warmup 2  (mean per dispatch, summed over the device; SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles, SQ_VALU_MFMA_BUSY_CYCLES = 32 x MFMA count)";
+{ hdr "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -- python3 bench.py --full --no-cpu --no-secondary --steps 3 --warmup 2  (mean per dispatch, summed over the device; SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles, SQ_VALU_MFMA_BUSY_CYCLES = 32 x MFMA count)";
   python tools/pmc_summary.py $SDB | grep -E "$K"; echo "# the same with --numerics bf16x3"; python tools/pmc_summary.py $XDB | grep -E "$K";
   echo "# --pmc FETCH_SIZE (own pass, KiB, raw)"; python tools/pmc_summary.py $FDB | grep -E "$K"; echo "# --pmc WRITE_SIZE (own pass, KiB)"; python tools/pmc_summary.py $WDB | grep -E "$K"; } > $PROF/${TAG}_vit224_gemm_pmc.txt
 python tools/make_traffic.py $FDB $WDB $PROF/${TAG}_vit224_gemm_traffic.json > /dev/null 2>&1 || fail "make_traffic failed"
 K2="maf_sample|smpl_|regressor_|tz_|attention|layernorm_blk|split3"
-{ hdr "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --workload whmr --eager --no-cpu --no-parity --steps 3 --warmup 2; mean per dispatch, summed over the device, KiB; HBM-side bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 on gfx950 (MI355X_MICROARCH.md)";
+{ hdr "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --workload whmr --eager --no-cpu --no-parity --steps 3 --warmup 2; mean per dispatch, summed over the device, KiB; HBM-side bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 on gfx950 (MI355X_MICROARCH.md)";
   echo "# FETCH_SIZE"; python tools/pmc_summary.py $WF | grep -E "$K2"; echo "# WRITE_SIZE"; python tools/pmc_summary.py $WW | grep -E "$K2"; } > $PROF/${TAG}_whmr_pmc.txt
 rm -rf $OUT/${TAG}_pmc_*
 for f in $PROF/*; do [ -s $f ] || fail "empty evidence file $f"; done
