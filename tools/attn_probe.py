@@ -1,5 +1,5 @@
-"""Attention core timing at the two ViT-B shapes (batch 64, 12 heads): row-major chunked / single-pass kernels, the blocked-layout kernel and
-its staging-only / key-loop-only ablations (wrong results, timing only)."""
+"""Attention core timing at the two ViT-B shapes (batch 64, 12 heads): row-major chunked / single-pass kernels, the blocked-layout kernels and
+the fp32 kernels."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,12 +24,8 @@ for N in (196, 192):
     ob = torch.empty((B * N + 31) // 32, 96, 32, 8, device=dev, dtype=torch.bfloat16)
     L.attention_set_variant(1)
     print('N=%d blocked, persistent 16-row-tile kernel (round 5): %.1f us' % (N, timeit(lambda: L.attention_blk(qb, ob, B, N, 12, 0.125))))
-    for var, name in ((1 | 2, 'no operand traffic after the first item'), (1 | 4, 'no arithmetic after the first item'), (1 | 2 | 4, 'neither')):
-        L.attention_set_variant(var)
-        print('N=%d blocked, persistent kernel, %s: %.1f us' % (N, name, timeit(lambda: L.attention_blk(qb, ob, B, N, 12, 0.125))))
-    for var, name in ((1 | 16, 'round-2 kernel, full'), (1 | 16 | 4, 'round-2 kernel, staging only (no key loop)'), (1 | 16 | 2, 'round-2 kernel, key loop only (no staging)'), (1 | 16 | 2 | 4, 'round-2 kernel, neither (launch + Q load + store)')):
-        L.attention_set_variant(var)
-        print('N=%d blocked %s: %.1f us' % (N, name, timeit(lambda: L.attention_blk(qb, ob, B, N, 12, 0.125))))
+    L.attention_set_variant(1 | 16)
+    print('N=%d blocked, round-2 kernel: %.1f us' % (N, timeit(lambda: L.attention_blk(qb, ob, B, N, 12, 0.125))))
 L.attention_set_variant(1)
 for N in (196, 192):
     q32 = torch.randn(B, N, 2304, device=dev)

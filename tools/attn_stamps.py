@@ -20,21 +20,18 @@ for _ in range(5):
     L.attention_blk(qb, ob, B, N, 12, 0.125)
 torch.cuda.synchronize()
 buf = torch.zeros(4 * 16 * 8, dtype=torch.int64, device=dev)
-for abl, name in ((0, 'full'), (2, 'no operand traffic after the first item'), (4, 'no arithmetic after the first item')):
-    buf.zero_()
-    lib.whmr_debug_att16_stamps(buf.data_ptr())
-    L.attention_set_variant(1 | abl)
-    L.attention_blk(qb, ob, B, N, 12, 0.125)
-    torch.cuda.synchronize()
-    lib.whmr_debug_att16_stamps(None)
-    L.attention_set_variant(1)
-    d = buf.cpu().view(4, 16, 8)
-    t0 = d[0, :, 0][d[0, :, 0] > 0].min().item()
-    print('# %s; N = %d: wave x [barrier passed | DMA issued | S^T done | softmax done | PV done | stores issued | next operands landed], shader cycles since the workgroup passed its first barrier' % (name, N))
-    for it in range(4):
-        if d[it, 0, 0] == 0:
+buf.zero_()
+lib.whmr_debug_att16_stamps(buf.data_ptr())
+L.attention_blk(qb, ob, B, N, 12, 0.125)
+torch.cuda.synchronize()
+lib.whmr_debug_att16_stamps(None)
+d = buf.cpu().view(4, 16, 8)
+t0 = d[0, :, 0][d[0, :, 0] > 0].min().item()
+print('# N = %d: wave x [barrier passed | DMA issued | S^T done | softmax done | PV done | stores issued | next operands landed], shader cycles since the workgroup passed its first barrier' % N)
+for it in range(4):
+    if d[it, 0, 0] == 0:
+        continue
+    for w in range(16):
+        if d[it, w, 0] == 0:
             continue
-        for w in range(16):
-            if d[it, w, 0] == 0:
-                continue
-            print('item %d wave %2d: ' % (it, w) + ' '.join('%7d' % (int(v) - t0 if v else -1) for v in d[it, w, :7]))
+        print('item %d wave %2d: ' % (it, w) + ' '.join('%7d' % (int(v) - t0 if v else -1) for v in d[it, w, :7]))

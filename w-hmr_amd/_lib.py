@@ -93,7 +93,6 @@ _SIGS = {
     'whmr_gemm_blk': [C.POINTER(WhmrGemmBlk), _P],
     'whmr_gemm_blk_tile': [C.POINTER(WhmrGemmBlk), _I, _P],
     'whmr_gemm_blk_set_tile': [_I, _I],
-    'whmr_gemm_blk_chain': [C.POINTER(WhmrGemmBlk), C.POINTER(WhmrGemmBlk), _P, _P, _P],
     'whmr_layernorm_blk': [_P, _P, _P, _P, _I, _I, _F, _I, _P],
     'whmr_gemm_blk_mx': [C.POINTER(WhmrGemmBlkMx), _P],
     'whmr_quantize_mx': [_P, _I, _P, _P, _I, _I, _P],
@@ -232,7 +231,7 @@ _SIDE_STREAMS = {}
 
 def side_stream(device, slot):
     """The package's side streams: FOUR per device, created together at the first request and shared by every user (slot 0: the heavy chain of the
-    forward / training graph, 1: camera head | Tz head's tail, 2: the ViT backward's weight-gradient stream, graph warm-ups, probes of bench.py,
+    forward / training graph, 1: camera head | Tz head's tail, 2: graph warm-ups, probes of bench.py,
     3: ClockProbe -- nothing else, its wave spins until it is released).  torch hands every ``torch.cuda.Stream()`` another of its 32 pooled HIP
     streams and HIP spreads those over a few hardware queues: a process that had created a dozen streams (the default bench.py run: graphs, camera
     streams, probes) ran the training step 0.6 ms slower than a fresh one -- its side streams shared hardware queues.  Roles that share a slot never
@@ -438,42 +437,6 @@ def gemm_blk(a, w, out, M, **kw):
         return out
     _check(lib().whmr_gemm_blk(C.byref(p), _stream()), 'whmr_gemm_blk')
     return out
-
-
-_CHAIN_SCRATCH = {}
-
-
-def gemm_blk_chain(fc1, fc2):
-    """PILOT (round 6): the fc1 -> fc2 pair of a transformer layer as ONE persistent launch (whmr_gemm_blk_chain).  fc1 / fc2: dicts of gemm_blk's
-    arguments (a, w, out, M, + keywords); fc2['a'] must be fc1['out'].  -> True when the pair was launched that way, False when the C entry does not
-    take the pair (the caller then issues the two launches).  The device-side error flag (a wait that hit its limit) is readable as ``chain_error(dev)``."""
-    f1, f2 = dict(fc1), dict(fc2)
-    p1, x31, N1, K1 = _blk_desc(f1.pop('a'), f1.pop('w'), f1.pop('out'), f1.pop('M'), **f1)
-    p2, x32, N2, K2 = _blk_desc(f2.pop('a'), f2.pop('w'), f2.pop('out'), f2.pop('M'), **f2)
-    if x31 or x32:
-        return False
-    dev = fc1['a'].device
-    sc = _CHAIN_SCRATCH.get(dev)
-    if sc is None:
-        sc = _CHAIN_SCRATCH[dev] = (torch.zeros(4096, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
-    if (p1.M + 319) // 320 > sc[0].numel():
-        return False
-    ev = _profile_begin()
-    rc = lib().whmr_gemm_blk_chain(C.byref(p1), C.byref(p2), sc[0].data_ptr(), sc[1].data_ptr(), _stream())
-    if rc == 1:                                  # hipErrorInvalidValue: not a pair the pilot takes, nothing was launched
-        return False
-    _check(rc, 'whmr_gemm_blk_chain')
-    if ev is not None:                           # one launch, two products: booked as two GEMM rows of half the span each
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        PROFILE.append(('gemm_bf16_chain', 2.0 * p1.M * (N1 * K1 + N2 * K2), ev, e1))
-    return True
-
-
-def chain_error(device):
-    """1 when a wait of a chained launch on ``device`` ever ran into its time limit (synchronises)"""
-    sc = _CHAIN_SCRATCH.get(device)
-    return 0 if sc is None else int(sc[1].item())
 
 
 def _blk_desc(a, w, out, M, bias=None, epi=EPI_BF16, res=None, res_rows=0, tile=0, xhat=None, stats_out=None, stats_in=None, colsum=None,
@@ -1222,9 +1185,9 @@ def attention_x3_set_variant(old_kernel):
 
 
 def attention_set_variant(chunked):
-    """bit 0: 1 = chunked online-softmax bf16 attention kernel (default), 0 = single-pass kernel; bits 1-2: timing ablations of the blocked kernels
-    (wrong results); bit 3 set: fp32 attention on the VALU kernel instead of the matrix-pipe one; bit 4 set: the blocked bf16 attention on the
-    round-2 kernel instead of the persistent 16-row-tile one (A/B measurements, tests)."""
+    """bit 0: 1 = chunked online-softmax bf16 attention kernel (default), 0 = single-pass kernel; bit 3 set: fp32 attention on the VALU kernel
+    instead of the matrix-pipe one; bit 4 set: the blocked bf16 attention on the round-2 kernel instead of the persistent 16-row-tile one (A/B
+    measurements, tests)."""
     _check(lib().whmr_attention_set_variant(int(chunked)), 'whmr_attention_set_variant')
 
 

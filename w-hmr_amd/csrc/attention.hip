@@ -159,7 +159,7 @@ __device__ __forceinline__ size_t blk_elem(int m, int col8, int ld8) { return ((
 
 template <int NKT, bool BLK = false>
 __global__ __launch_bounds__(NKT * 64, 4) void attention_bf16_chunk_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                                           int N, int H, float scale, float* __restrict__ lse, int abl = 0) {
+                                                                           int N, int H, float scale, float* __restrict__ lse) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NPAD = NKT * 32;
     constexpr int VS = NPAD + 4;
@@ -179,39 +179,35 @@ __global__ __launch_bounds__(NKT * 64, 4) void attention_bf16_chunk_kernel(const
         // workgroup's lifetime (round 3: 24.9 -> see DESIGN 6).
         uint4 kreg[4], vreg[2][2];
         const int qr = (wave * 32 + l31 > N - 1) ? N - 1 : wave * 32 + l31;
-        if (!(abl & 2)) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = tid + i * (NKT * 64), key = c % NPAD, ch = c / NPAD;
-                kreg[i] = make_uint4(0, 0, 0, 0);
-                if (key < N) kreg[i] = *(const uint4*)(qkv + blk_elem(m_img + key, (C + h * 64) / 8 + ch, ld8));
-            }
+        for (int i = 0; i < 4; ++i) {
+            const int c = tid + i * (NKT * 64), key = c % NPAD, ch = c / NPAD;
+            kreg[i] = make_uint4(0, 0, 0, 0);
+            if (key < N) kreg[i] = *(const uint4*)(qkv + blk_elem(m_img + key, (C + h * 64) / 8 + ch, ld8));
+        }
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int c = tid + i * (NKT * 64), kp = c % (NPAD / 2), ch = c / (NPAD / 2), k0 = 2 * kp;
-                vreg[i][0] = vreg[i][1] = make_uint4(0, 0, 0, 0);
-                if (k0 < N) vreg[i][0] = *(const uint4*)(qkv + blk_elem(m_img + k0, (2 * C + h * 64) / 8 + ch, ld8));
-                if (k0 + 1 < N) vreg[i][1] = *(const uint4*)(qkv + blk_elem(m_img + k0 + 1, (2 * C + h * 64) / 8 + ch, ld8));
-            }
+        for (int i = 0; i < 2; ++i) {
+            const int c = tid + i * (NKT * 64), kp = c % (NPAD / 2), ch = c / (NPAD / 2), k0 = 2 * kp;
+            vreg[i][0] = vreg[i][1] = make_uint4(0, 0, 0, 0);
+            if (k0 < N) vreg[i][0] = *(const uint4*)(qkv + blk_elem(m_img + k0, (2 * C + h * 64) / 8 + ch, ld8));
+            if (k0 + 1 < N) vreg[i][1] = *(const uint4*)(qkv + blk_elem(m_img + k0 + 1, (2 * C + h * 64) / 8 + ch, ld8));
         }
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) qf[kk] = *(const bf16x8_t*)(qkv + blk_elem(m_img + qr, (h * 64) / 8 + kk * 2 + hi, ld8));
-        if (!(abl & 2)) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = tid + i * (NKT * 64), key = c % NPAD, ch = c / NPAD;
-                *(uint4*)(Ks + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[i];
-            }
+        for (int i = 0; i < 4; ++i) {
+            const int c = tid + i * (NKT * 64), key = c % NPAD, ch = c / NPAD;
+            *(uint4*)(Ks + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[i];
+        }
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int c = tid + i * (NKT * 64), kp = c % (NPAD / 2), ch = c / (NPAD / 2), k0 = 2 * kp;
-                const uint4 v0 = vreg[i][0], v1 = vreg[i][1];
-                const uint32_t a[4] = {v0.x, v0.y, v0.z, v0.w}, bb[4] = {v1.x, v1.y, v1.z, v1.w};
+        for (int i = 0; i < 2; ++i) {
+            const int c = tid + i * (NKT * 64), kp = c % (NPAD / 2), ch = c / (NPAD / 2), k0 = 2 * kp;
+            const uint4 v0 = vreg[i][0], v1 = vreg[i][1];
+            const uint32_t a[4] = {v0.x, v0.y, v0.z, v0.w}, bb[4] = {v1.x, v1.y, v1.z, v1.w};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    *(uint32_t*)(Vt + (ch * 8 + 2 * e) * VS + k0) = (a[e] & 0xffffu) | (bb[e] << 16);
-                    *(uint32_t*)(Vt + (ch * 8 + 2 * e + 1) * VS + k0) = (a[e] >> 16) | (bb[e] & 0xffff0000u);
-                }
+            for (int e = 0; e < 4; ++e) {
+                *(uint32_t*)(Vt + (ch * 8 + 2 * e) * VS + k0) = (a[e] & 0xffffu) | (bb[e] << 16);
+                *(uint32_t*)(Vt + (ch * 8 + 2 * e + 1) * VS + k0) = (a[e] >> 16) | (bb[e] & 0xffff0000u);
             }
         }
 #pragma unroll
@@ -254,7 +250,7 @@ __global__ __launch_bounds__(NKT * 64, 4) void attention_bf16_chunk_kernel(const
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[dh][r] = 0.f;
 #pragma unroll 1
-    for (int c0 = (abl & 4) ? NKT : 0; c0 < NKT; c0 += 2) {
+    for (int c0 = 0; c0 < NKT; c0 += 2) {
         const int nt = (NKT - c0) < 2 ? (NKT - c0) : 2;
         f32x16_t s[2];
 #pragma unroll
@@ -836,12 +832,11 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
 }
 
 static int g_attn_chunked = 1;      // whmr_attention_set_variant: bit 0: 1 = chunked online-softmax kernel (default), 0 = single pass
-static int g_attn_abl = 0;          // bits 1-2 (timing probes only, wrong results): 2 = skip the K / V staging, 4 = skip the key loop
 static int g_attn_f32_mfma = 1;     // bit 3 SET switches the fp32 attention back to the VALU kernel (A/B, tests)
 static int g_attn_blk_old = 0;      // bit 4 SET: the blocked bf16 attention on the round-2 kernel (one workgroup per (image, head), 32-row tiles) instead of
                                     // the persistent 16-row-tile kernel of attention_blk16.hip (A/B, tests)
-extern "C" int whmr_attention_set_variant(int v) { g_attn_chunked = v & 1; g_attn_abl = v & 6; g_attn_f32_mfma = !(v & 8); g_attn_blk_old = (v >> 4) & 1; return 0; }
-int whmr_attention_blk16_launch(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t st, int abl);      // attention_blk16.hip
+extern "C" int whmr_attention_set_variant(int v) { g_attn_chunked = v & 1; g_attn_f32_mfma = !(v & 8); g_attn_blk_old = (v >> 4) & 1; return 0; }
+int whmr_attention_blk16_launch(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t st);      // attention_blk16.hip
 
 template <int NKT>
 static int launch_bf16(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t st, float* lse = nullptr) {
@@ -862,7 +857,7 @@ static int launch_bf16_blk(const void* qkv, void* out, int B, int N, int H, floa
     constexpr int NPAD = NKT * 32;
     const size_t lds = (size_t)NPAD * 128 + 64 * (NPAD + 4) * 2;
     hipLaunchKernelGGL((attention_bf16_chunk_kernel<NKT, true>), dim3(B * H), dim3(NKT * 64), lds, st, (const bf16_t*)qkv, (bf16_t*)out, N, H, scale,
-                       (float*)nullptr, g_attn_abl);
+                       (float*)nullptr);
     WHMR_CHECK_LAUNCH();
     return 0;
 }
@@ -871,7 +866,7 @@ static int launch_bf16_blk(const void* qkv, void* out, int B, int N, int H, floa
 extern "C" int whmr_attention_blk(const void* qkv, void* out, int B, int N, int H, float scale, void* stream) {
     if (B <= 0 || N <= 64 || N > 256 || H <= 0 || scale <= 0.f) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    if (!g_attn_blk_old && N <= 240) return whmr_attention_blk16_launch(qkv, out, B, N, H, scale, st, g_attn_abl);
+    if (!g_attn_blk_old && N <= 240) return whmr_attention_blk16_launch(qkv, out, B, N, H, scale, st);
     switch ((N + 31) / 32) {
         case 3: return launch_bf16_blk<3>(qkv, out, B, N, H, scale, st);
         case 4: return launch_bf16_blk<4>(qkv, out, B, N, H, scale, st);

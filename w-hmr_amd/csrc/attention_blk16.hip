@@ -93,7 +93,7 @@ __device__ __forceinline__ size_t att_piece(int m, int col8, int l8) { return ((
 
 template <int NQT>
 __global__ __launch_bounds__((NQT + att16_cfg<NQT>::NL) * 64) void attention_blk16_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, int items, int N, int H,
-                                                                    float scale, int abl) {
+                                                                    float scale) {
     using cfg = att16_cfg<NQT>;
     constexpr int NK2 = cfg::NK2, KP = cfg::KP, VP = cfg::VP;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -285,8 +285,6 @@ __global__ __launch_bounds__((NQT + att16_cfg<NQT>::NL) * 64) void attention_blk
 
     int item = blockIdx.x, buf = 0;
     if (item >= items) return;
-    // abl (whmr_attention_set_variant bits 1-2, timing probes with WRONG results): 2 = no operand traffic after the first item (every item is
-    // computed on the first one's K / V / Q), 4 = no arithmetic (operand traffic, barriers and the stores of the first item only)
     if (wave >= NQT) {
         // ---- LOADER waves (NL of them, every NL-th piece each): all LDS-DMA pieces of an item.  Issuing them blocks for as long as the memory pipeline
         // takes to accept ~80 KiB per CU with every CU bursting at once (stamps: 3 300 - 6 100 cycles when the compute waves issued their own
@@ -300,10 +298,8 @@ __global__ __launch_bounds__((NQT + att16_cfg<NQT>::NL) * 64) void attention_blk
             __builtin_amdgcn_s_barrier();                  // B
             const int next = item + gridDim.x;
             if (next >= items) break;
-            if (!(abl & 2)) {
-                issue_q(next);
-                issue_dma(next, buf ^ 1);
-            }
+            issue_q(next);
+            issue_dma(next, buf ^ 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             item = next;
             buf ^= 1;
@@ -319,13 +315,12 @@ __global__ __launch_bounds__((NQT + att16_cfg<NQT>::NL) * 64) void attention_blk
         q[1] = att_read128<4 * KP * 16>(qa);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(q[0]), "+v"(q[1]));
         __builtin_amdgcn_s_barrier();                      // B
-        const int next = item + gridDim.x;
-        const bool more = next < items;
         ATT_STAMP(it, 1);
-        if (!(abl & 4) || item == (int)blockIdx.x) compute(item, (abl & 2) ? 0 : buf, q, it);
+        compute(item, buf, q, it);
         ATT_STAMP(it, 5);
-        if (!more) break;
-        item = next;
+        // (the next item after the compute: gridDim.x is a scalar load, and a wait for it drains the LDS reads the first MFMAs overlap)
+        item += gridDim.x;
+        if (item >= items) break;
         buf ^= 1;
     }
 }
@@ -609,7 +604,7 @@ static int att16_cus() {
 }
 
 template <int NQT>
-static int att16_launch(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t st, int abl) {
+static int att16_launch(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t st) {
     using cfg = att16_cfg<NQT>;
     auto kern = attention_blk16_kernel<NQT>;
     static bool attr_done = false;
@@ -621,25 +616,25 @@ static int att16_launch(const void* qkv, void* out, int B, int N, int H, float s
     const int items = B * H;
     const int cus = att16_cus();
     const int grid = items < cus ? items : cus;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3((NQT + cfg::NL) * 64), cfg::LDS, st, (const bf16_t*)qkv, (bf16_t*)out, items, N, H, scale, abl);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3((NQT + cfg::NL) * 64), cfg::LDS, st, (const bf16_t*)qkv, (bf16_t*)out, items, N, H, scale);
     WHMR_CHECK_LAUNCH();
     return 0;
 }
 
 // called by whmr_attention_blk (attention.hip) for 64 < N <= 256
-int whmr_attention_blk16_launch(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t st, int abl) {
+int whmr_attention_blk16_launch(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t st) {
     switch ((N + 15) / 16) {
-        case 5: return att16_launch<5>(qkv, out, B, N, H, scale, st, abl);
-        case 6: return att16_launch<6>(qkv, out, B, N, H, scale, st, abl);
-        case 7: return att16_launch<7>(qkv, out, B, N, H, scale, st, abl);
-        case 8: return att16_launch<8>(qkv, out, B, N, H, scale, st, abl);
-        case 9: return att16_launch<9>(qkv, out, B, N, H, scale, st, abl);
-        case 10: return att16_launch<10>(qkv, out, B, N, H, scale, st, abl);
-        case 11: return att16_launch<11>(qkv, out, B, N, H, scale, st, abl);
-        case 12: return att16_launch<12>(qkv, out, B, N, H, scale, st, abl);
-        case 13: return att16_launch<13>(qkv, out, B, N, H, scale, st, abl);
-        case 14: return att16_launch<14>(qkv, out, B, N, H, scale, st, abl);
-        case 15: return att16_launch<15>(qkv, out, B, N, H, scale, st, abl);
+        case 5: return att16_launch<5>(qkv, out, B, N, H, scale, st);
+        case 6: return att16_launch<6>(qkv, out, B, N, H, scale, st);
+        case 7: return att16_launch<7>(qkv, out, B, N, H, scale, st);
+        case 8: return att16_launch<8>(qkv, out, B, N, H, scale, st);
+        case 9: return att16_launch<9>(qkv, out, B, N, H, scale, st);
+        case 10: return att16_launch<10>(qkv, out, B, N, H, scale, st);
+        case 11: return att16_launch<11>(qkv, out, B, N, H, scale, st);
+        case 12: return att16_launch<12>(qkv, out, B, N, H, scale, st);
+        case 13: return att16_launch<13>(qkv, out, B, N, H, scale, st);
+        case 14: return att16_launch<14>(qkv, out, B, N, H, scale, st);
+        case 15: return att16_launch<15>(qkv, out, B, N, H, scale, st);
     }
     return -1;                  // N > 240: 16 query tiles + the loader wave exceed 1024 threads -- the caller keeps the round-2 kernel
 }

@@ -101,14 +101,12 @@ class ViT(nn.Module):
         self._wcache = {}
         self._ws = {}
         self.blocked = True                 # bf16 inference on the blocked-layout kernels when the shapes allow it
-        self.chain_mlp = os.environ.get('WHMR_BLK_CHAIN', '0') != '0'      # pilot: fc1 -> fc2 as one persistent launch (whmr_gemm_blk_chain)
         # pilot, off by default: the four Linears of every block as MXFP8 GEMMs (_forward_tokens_mx) in the bf16 inference path.  NOT a numerics mode:
         # measured slower than bf16 and ~13x its error (profiles/r07_mxfp8_first_measurement.txt); kept to measure the FP8 kernels in the model
         self.mx_pilot = os.environ.get('WHMR_MX_PILOT', '0') != '0'
         self.blocked_min_tokens = 2048      # ... and the batch has at least this many tokens (set 0 to force the blocked path)
         self.x3_min_tokens = 320            # bf16x3: below this many tokens (one 224^2 / 256x192 crop) the exact-f32 path is the faster parity-grade one
-        self.ln_fold = True                 # ... with norm1 / norm2 folded into the qkv / fc1 GEMMs (no LayerNorm pass inside the blocks)
-        self.ln_fold_x3 = os.environ.get('WHMR_X3_FOLD', '1') != '0'      # the same fold in the bf16x3 pipeline (A/B: tools/r3_x3ab.sh)
+        self.ln_fold = True                 # ... with norm1 / norm2 folded into the qkv / fc1 GEMMs (no LayerNorm pass inside the blocks; bf16 and bf16x3)
 
     # ------------------------------------------------------------------ weight / workspace caches
     def _w(self, p, shape=None, eff=None):
@@ -274,20 +272,14 @@ class ViT(nn.Module):
                            stats_out=st[cur ^ 1], shift=sh[cur], shift_stats=None if bi == 0 else st[cur], shift_out=sh[cur ^ 1])
                 cur ^= 1
                 w1, s1, c1 = self._wfold(blk.mlp.fc1, blk.norm2)
-                fc1 = dict(a=h, w=w1, out=hid, M=M, bias=c1, epi=L.EPI_BF16_GELU, stats_in=st[cur], colsum=s1, ln_eps=1e-6)
-                last = bi + 1 == nblk
-                if last:
-                    fc2 = dict(a=hid, w=self._wblk(blk.mlp.fc2.weight), out=t, M=M, bias=blk.mlp.fc2.bias, epi=L.EPI_F32_RES, res=t)
+                L.gemm_blk(h, w1, hid, M, bias=c1, epi=L.EPI_BF16_GELU, stats_in=st[cur], colsum=s1, ln_eps=1e-6)
+                w2 = self._wblk(blk.mlp.fc2.weight)
+                if bi + 1 == nblk:
+                    L.gemm_blk(hid, w2, t, M, bias=blk.mlp.fc2.bias, epi=L.EPI_F32_RES, res=t)
                 else:
-                    fc2 = dict(a=hid, w=self._wblk(blk.mlp.fc2.weight), out=t, M=M, bias=blk.mlp.fc2.bias, epi=L.EPI_F32_RES, res=t, xhat=h,
+                    L.gemm_blk(hid, w2, t, M, bias=blk.mlp.fc2.bias, epi=L.EPI_F32_RES, res=t, xhat=h,
                                stats_out=st[cur ^ 1], shift=sh[cur], shift_stats=st[cur], shift_out=sh[cur ^ 1])
                     cur ^= 1
-                # (pilot, WHMR_BLK_CHAIN=1: the pair as one persistent launch with arrive counters -- same bits; off by default, DESIGN 8 item 2.
-                #  fc2 overwrites h -- fc1's A operand -- with the next LayerNorm's operand copy: safe inside the chain, because an fc2 tile starts only when
-                #  ALL fc1 column tiles of its row panel, the only readers of those rows of h, have arrived)
-                if not (self.chain_mlp and L.gemm_blk_chain(fc1, fc2)):
-                    L.gemm_blk(**fc1)
-                    L.gemm_blk(**fc2)
             out = torch.empty((M, D), dtype=f32, device=dev)
             L.layernorm_blk(t, self.last_norm.weight, self.last_norm.bias, out, M, 1e-6, out_std=True)
             return out
@@ -392,7 +384,7 @@ class ViT(nn.Module):
         L.gemm_blk(cols[0], w[0], t, M, bias=self.patch_embed.proj.bias, epi=L.EPI_F32_POS, res=pos, res_rows=N, a_lo=cols[1], w_lo=w[1])
         hd = self.blocks[0].mlp.fc1.weight.shape[0] if self.depth else D
         h, qkv, att, hid = pair('x3h', D), pair('x3qkv', 3 * D), pair('x3att', D), pair('x3hid', hd)
-        if self.ln_fold and self.ln_fold_x3 and D <= 1024 and self.depth:
+        if self.ln_fold and D <= 1024 and self.depth:
             # LayerNorm folded into the GEMM pair as in the bf16 pipeline, on operand PAIRS: the producers (proj, fc2) also emit the centred row
             # (x - s_m) split into hi / lo + its partial sums, the consumers (qkv, fc1) multiply it by the hi / lo pair of gamma o W and normalise
             # in their epilogue.  The first LayerNorm runs explicitly and seeds the shift.  Saves 2 x depth - 1 LayerNorm passes (13.5 us each).

@@ -373,8 +373,6 @@ class WHMR(nn.Module):
         self.overlap_camera = True          # cam_model on a side stream beside the backbone (joined before the global-orientation head)
         self.camera_launch = os.environ.get('WHMR_CAM_LAUNCH', 'early')    # where the camera branch's launches are issued: 'early' | 'vit' | 'loop' (A/B, see _forward_eval)
         self.overlap_tz = True              # Tz head on a side stream beside the regressor loop (its outputs finalized after the join)
-        self.smpl_offsets_x3 = os.environ.get('WHMR_SMPL_X3', '1') != '0'   # A/B: 0 keeps the exact-f32 offsets in every numerics mode
-        self.compose_tz = os.environ.get('WHMR_COMPOSE_TZ', '1') != '0'   # inference: the two Tz-head convolutions as ONE composed k25 / s6 convolution (False: the two-convolution form)
         self._tz_gemm_kw = {}               # explicit tile / split-K of the composed convolution's GEMM (A/B probes)
         self._tz_ones = {}
         # torch's DistributedDataParallel (the reference's wrap, core/trainer.py:84-86) re-broadcasts every module buffer before each forward.  Here
@@ -516,7 +514,7 @@ class WHMR(nn.Module):
         dev = f_nhwc.device
         assert (C, self.conv[1].weight.shape[0], self.conv[0].weight.shape[0]) == (256, 5, 64)
         H1, W1 = (H - 7) // 3 + 1, (W - 7) // 3 + 1
-        if self.compose_tz and W % 6 == 0:
+        if W % 6 == 0:                      # inference: the two convolutions as ONE composed k25 / s6 convolution (other widths: the two-convolution form)
             return self._tz_tokens_tail(self._tz_tokens_composed(f_nhwc, f_split), B, dev, self._tz_composed_operands()[1])
         w0, w1, bn4 = self._tz_operands()
         y0 = torch.empty(B, H1, W1, 128 if self.numerics == 'bf16x3' else 64, dtype=self._dt, device=dev)     # NHWC, mode dtype (feeds the 2nd conv)
@@ -657,7 +655,7 @@ class WHMR(nn.Module):
         with_aux = view == 'train'
         B, dev = x.shape[0], x.device
         # SMPL's pose-corrective offsets: split-bf16 MFMA operands in the bf16 / bf16x3 numerics (~3e-7 of a vertex), the exact f32 chain in fp32
-        self.regressor[0].smpl.offsets_x3 = self.numerics != 'fp32' and self.smpl_offsets_x3
+        self.regressor[0].smpl.offsets_x3 = self.numerics != 'fp32'
         # The camera-calibration ResNet-50 (whmr.py:509-522) only feeds the global-orientation head at the very end (whmr.py:630): it runs on a
         # SIDE stream beside the backbone / deconvs / regressor loop and is joined just before that head.  Its few-tile launches slot into the CUs
         # the big GEMM grids leave idle (tile-grid tails); under GraphedForward the fork / join become two branches of the captured graph.

@@ -14,13 +14,8 @@ autograd as driven by ``core/trainer.py:410-470``.  Maps are channels-last (NHWC
 """
 import torch
 
-import os
-
 from .. import _lib as L
 from ..parallel import sync_bn
-
-USE_TN = os.environ.get('WHMR_TN_GEMM', '1') != '0'      # weight gradients on the gathering TN kernel (A/B switch)
-
 
 _PHASE_INDEX = {}
 
@@ -102,7 +97,7 @@ def deconv_backward(saved, weight, dy, dt, need_dx=True, dx_dtype=None, dx_into=
     pad = 64 if dt == torch.bfloat16 else 8          # the bf16 GEMM needs K % 64 == 0; rows are zero-padded up to it
     dwm = torch.empty(Cin, 16 * Cout, dtype=torch.float32, device=dev)
     x2 = x.view(M, Cin)
-    if USE_TN and L.conv_dw_tn_ok(x2, dz):
+    if L.conv_dw_tn_ok(x2, dz):
         # the gathering TN kernel reads X and dZ as they are (no transposed X, no 16-tap transposed column matrix of dZ: 1.6 GB at stage 3)
         L.conv_dw_tn(x2, dz, dwm, H, W, 4, 4, 2, 1)
     else:

@@ -14,8 +14,6 @@ import os
 
 from .. import _lib as L
 
-USE_TN = os.environ.get('WHMR_TN_GEMM', '1') != '0'      # weight gradients on the (gathering) TN kernel (A/B switch)
-
 
 def _f32(t):
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
@@ -254,7 +252,7 @@ class ConvNHWCFn(torch.autograd.Function):
         pad = 64 if dt == torch.bfloat16 else 8
         dx = dw = db = None
         same = S == 1 and OH == IH and OW == IW
-        if ctx.needs_input_grad[1] and USE_TN and dt == torch.bfloat16 and Cin % 256 == 0 and M % 32 == 0 and x.is_contiguous():
+        if ctx.needs_input_grad[1] and dt == torch.bfloat16 and Cin % 256 == 0 and M % 32 == 0 and x.is_contiguous():
             # gathering TN kernel: dW[co, (ky, kx, ci)] = sum_m dY[m, co] . X[pixel(m) + tap, ci] from dY and X as they are -- no transposed
             # dY, no (transposed) column matrix of X.  dY is widened to a multiple of 128 columns (the kernel's smallest row tile) if need be.
             na = (npad + TN_ROW_PAD - 1) // TN_ROW_PAD * TN_ROW_PAD

@@ -102,7 +102,7 @@ def vit_forward_train(m, x):
         L.layernorm(a.t_mid, blk.norm2.weight, blk.norm2.bias, a.h2, 1e-6)
         a.pre = torch.empty(M, hidden, dtype=dt, device=dev)
         a.hid = torch.empty_like(a.pre)
-        if FUSE_GELU and dt == torch.bfloat16:
+        if dt == torch.bfloat16:
             # fc1's epilogue leaves both the pre-activation (the backward needs it) and its GELU: no separate pass over the [M, 4D] map
             L.gemm(a.h2, wop(blk.mlp.fc1.weight), a.hid, bias=blk.mlp.fc1.bias, act=L.ACT_GELU, pre_out=a.pre)
         else:
@@ -141,19 +141,9 @@ def _attention_bwd(qkv, d_att, B, N, H, dh, scale, dt):
     return dq if dt == torch.float32 else L.cast_bf16(dq)
 
 
-# weight-gradient branch of the ViT backward on a side stream (A/B switch, OFF by default).  With the transposed-copy dW path it hid the
-# memory-bound transposes beside the dX GEMMs (backbone-only step, 224^2, batch 64: 15.25 -> 14.23 ms); the TN kernel removes those
-# transposes altogether (15.16 -> 14.15 ms in line) and then the second stream buys nothing (14.08) -- and inside the full W-HMR step it costs
-# 0.3-0.6 ms (256x192, eager and graph-replayed).  The same treatment of the deconv / conv nodes measured neutral to -3 % and is not in the tree.
-OVERLAP_DW = os.environ.get('WHMR_OVERLAP_DW', '0') != '0'
-FUSE_GELU = os.environ.get('WHMR_FUSE_GELU', '1') != '0'      # bf16 mode: GELU inside fc1's epilogue (pre-activation kept as a second output) and its
-                                                               # backward inside fc2's data-gradient epilogue (A/B switch)
-USE_TN = os.environ.get('WHMR_TN_GEMM', '1') != '0'          # weight gradients on whmr_gemm_tn_bf16 (A/B switch; fp32 mode and odd shapes keep the transposed-copy path)
 # the four weight gradients of a layer in ONE launch of the TN kernel (whmr_gemm_tn_bf16_group: two K slices instead of 7-28 per product, a quarter of
 # the fp32 partial-tile traffic); A/B switch
 GROUP_DW = os.environ.get('WHMR_TN_GROUP', '1') != '0'
-def _side_stream(dev):
-    return L.side_stream(dev, 2)
 
 
 @torch.no_grad()
@@ -172,17 +162,6 @@ def vit_backward(m, s, dout):
         w = p.detach()
         return L.transpose_cast(w.reshape(shape) if shape is not None else w, dt, pad_to=1)
 
-    # The weight-gradient branch of every Linear (transpose dY (+ bias column sums), transpose X, dW = dY^T . X) only depends on dY and the saved
-    # input, and nothing on the critical path (dX -> GELU / attention / LayerNorm backward -> next dX) waits for it: it runs on a SIDE stream.
-    # Its memory-bound transposes then sit beside the MFMA-bound dX GEMMs of the main stream on the same CUs, and either branch fills the CUs the
-    # other one's tile-grid tails leave idle.  Joined at the end of the node; same kernels, same bits.
-    main = torch.cuda.current_stream(dev)
-    side = _side_stream(dev) if OVERLAP_DW else None
-    capturing = torch.cuda.is_current_stream_capturing()
-    side_made = []
-    if side is not None:
-        side.wait_stream(main)
-
     pending = []                                                                       # weight-gradient products of the current layer (GROUP_DW)
 
     def run_pending():
@@ -198,48 +177,35 @@ def vit_backward(m, s, dout):
     def dw_branch(dy_op, x_saved, lin):
         w = lin.weight
         n_out, k_in = dy_op.shape[1], x_saved.shape[1]
-        if USE_TN and L.gemm_tn_ok(dy_op, x_saved):
+        if L.gemm_tn_ok(dy_op, x_saved):
             # dW = dY^T . X straight from the token-major operands (gemm_tn.hip: transposing LDS reads) -- no transposed copies
             db = None
             if lin.bias is not None:                                                   # column sums of dY ride along in the same kernel
                 db = torch.empty(n_out, **f32)
                 grads[lin.bias] = db
-                side_made.append(db)
             dw = torch.empty(n_out, k_in, **f32)
-            if GROUP_DW and side is None and n_out % 256 == 0:
+            if GROUP_DW and n_out % 256 == 0:
                 pending.append((dy_op, x_saved, dw, db))                               # launched with the layer's other three (run_pending)
             else:
                 L.gemm_tn(dy_op, x_saved, dw, db=db)
             grads[w] = dw.view_as(w)
-            side_made.append(dw)
             return
+        # fp32 mode and shapes the TN kernel refuses: transposed copies of dY and X, then a plain GEMM
         if lin.bias is not None:                                                       # db from the same pass that transposes dY
             db = torch.empty(n_out, **f32)
             dyt = L.transpose_colsum(dy_op, db, pad_to=mpad)                           # [Nout, Mpad]
             grads[lin.bias] = db
-            side_made.append(db)
         else:
             dyt = L.transpose_cast(dy_op, dt, pad_to=mpad)
         xt = L.transpose_cast(x_saved, dt, pad_to=mpad)                                # [Kin, Mpad]
         dw = torch.empty(n_out, k_in, **f32)
         L.gemm(dyt, xt, dw)
         grads[w] = dw.view_as(w)
-        side_made.append(dw)
 
     def linear_bwd(dy_op, x_saved, lin, need_dx=True, wshape=None, dx_dtype=torch.float32, gelu_bwd_of=None):
         """dy_op [M, Nout] (compute dtype), x_saved [M, Kin] -> dx [M, Kin] (fp32 unless dx_dtype); records dW, db.
         gelu_bwd_of: the pre-activation whose GELU produced x_saved -- dx is then multiplied by gelu'(pre) in the epilogue (= d pre)."""
-        if side is None:
-            dw_branch(dy_op, x_saved, lin)
-        else:
-            ev = torch.cuda.Event()
-            ev.record(main)                                                            # dY (and the saved input) are complete on the main stream
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                dw_branch(dy_op, x_saved, lin)
-            if not capturing:                                                          # main-stream tensors read by the side stream
-                dy_op.record_stream(side)
-                x_saved.record_stream(side)
+        dw_branch(dy_op, x_saved, lin)
         if not need_dx:
             return None
         w = lin.weight
@@ -249,8 +215,8 @@ def vit_backward(m, s, dout):
 
     # Early delivery to the data-parallel reducer (GradReducer.publish): everything in ``grads`` that belongs to finished blocks is handed over
     # in the order the parameters were registered (reverse = backward order inside a block), so that a full bucket's all-reduce runs on
-    # RCCL's stream beside the backward of the earlier blocks.  Only when the gradients are produced on the node's own stream.
-    sink = getattr(m, 'grad_sink', None) if side is None else None
+    # RCCL's stream beside the backward of the earlier blocks.
+    sink = getattr(m, 'grad_sink', None)
     published = set()
     order = {id(q): i for i, q in enumerate(m.parameters())}
 
@@ -268,7 +234,7 @@ def vit_backward(m, s, dout):
     # bf16 mode: every LayerNorm backward also writes the compute-dtype operand of the NEXT branch's backward GEMMs (dx times that branch's
     # stochastic-depth row factor) -- the cast / scale_rows_cast pass per branch (22 launches of 10 us per step) is a by-product of a pass that
     # holds the row in registers anyway
-    fuse_cast = FUSE_GELU and dt == torch.bfloat16
+    fuse_cast = dt == torch.bfloat16
     rev = list(zip(reversed(list(m.blocks)), reversed(s.layers)))
 
     def operand():
@@ -285,7 +251,7 @@ def vit_backward(m, s, dout):
             dy = dy_next
         else:
             dy = _op(dt_grad, dt) if a.rs_mlp is None else L.scale_rows_cast(dt_grad, a.rs_mlp, dt)
-        if FUSE_GELU and dt == torch.bfloat16:
+        if fuse_cast:
             d_pre = linear_bwd(dy, a.hid, blk.mlp.fc2, dx_dtype=dt, gelu_bwd_of=a.pre)        # fc2's data gradient * gelu'(pre) in one pass
         else:
             d_hid = linear_bwd(dy, a.hid, blk.mlp.fc2, dx_dtype=dt)                        # only feeds the GELU backward: compute dtype
@@ -331,11 +297,6 @@ def vit_backward(m, s, dout):
     for q in list(grads):                                                              # delivered already: the node returns None for them
         if id(q) in published:
             grads[q] = None
-    if side is not None:                                                               # join: the gradients are consumed on the main stream
-        main.wait_stream(side)
-        if not capturing:
-            for t in side_made:
-                t.record_stream(main)
     return grads
 
 

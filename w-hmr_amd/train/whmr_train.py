@@ -53,13 +53,10 @@ def _projection(joints, cam):
     return torch.stack([x, y], dim=-1)
 
 
-CHAIN_GRADS = os.environ.get('WHMR_CHAIN_GRADS', '1') != '0'      # feature maps handed from consumer to consumer (A/B switch), see whmr_forward_train
-CHAIN_SAMPLER3 = os.environ.get('WHMR_CHAIN_SAMPLER3', '0') != '0'   # the stage-3 sampler behind the two heads in the last map's chain (A/B switch)
 FORK_SAMPLER3 = os.environ.get('WHMR_TRAIN_FORK3', '1') != '0'       # the stage-3 sampler's map gradient as per-point records added to the heads' gradient
 # the side stream's nodes ahead of the loop's in autograd's ready queue (see _backward_first).  Opt-in: -0.07 ms on the single-GPU step (three A/B rounds),
 # but +2.2 ms under torch's DistributedDataParallel, whose reducer expects gradients in roughly reverse-forward order (22.7 -> 24.9 ms, one-rank RCCL group)
 HEAVY_FIRST = os.environ.get('WHMR_TRAIN_HEAVY_FIRST', '0') != '0'
-COMPOSE_TZ = os.environ.get('WHMR_TRAIN_COMPOSE_TZ', '1') != '0'     # bf16 numerics: the Tz head's two convolutions as one composed convolution (TzComposedFn)
 TZ_TAIL_STREAM = os.environ.get('WHMR_TRAIN_TZ_TAIL', '1') != '0'     # the Tz head's 5-token tail (a hundred tiny launches) on a stream of its own beside the IUV head
 OVERLAP_HEAVY = os.environ.get('WHMR_TRAIN_OVERLAP', '1') != '0'      # deconv 2 / 3 + Tz head + IUV head on a side stream beside the regressor loop
 _STREAM_WARNING_OFF = False
@@ -120,7 +117,7 @@ def tz_head_train(model, f_nhwc, passthrough=False, tail_stream=None):
     dt = model._dt
     B = f_nhwc.shape[0]
     f_next = None
-    if COMPOSE_TZ and dt == torch.bfloat16 and TzComposedFn.fits(f_nhwc):
+    if dt == torch.bfloat16 and TzComposedFn.fits(f_nhwc):
         # both convolutions as ONE composed convolution, gradients through the composed weight (heads_autograd.TzComposedFn)
         t = TzComposedFn.apply(f_nhwc, model.conv[0].weight, model.conv[1].weight, passthrough)
         t, f_next = t if passthrough else (t, None)
@@ -246,24 +243,24 @@ def whmr_forward_train(model, x, center, scale, bbox_height, orig_shape, bbox_in
     aux = bool(cfg.MODEL.PyMAF.AUX_SUPV_ON and hasattr(model, 'dp_head'))
     tz_grad = int(cfg.TRAIN.STAGE) != 1                                               # stage 1 trains the Tz head on a detached map
 
-    # Every feature map has two or three consumers (the next deconv stage or the two heads, and the stage's sampler).  With CHAIN_GRADS a map is
-    # handed from one consumer's node to the next (deconv / head convolution -> sampler; DeconvBNReLUFn / ConvNHWCFn ``passthrough``): in the
+    # Every feature map has two or three consumers (the next deconv stage or the two heads, and the stage's sampler).  A map is handed
+    # from one consumer's node to the next (deconv / head convolution -> sampler; DeconvBNReLUFn / ConvNHWCFn ``passthrough``): in the
     # backward pass each data gradient is then added, in the GEMM epilogue, to the gradient the consumers behind it left on the map, instead of
     # autograd summing full-size maps (two 0.2 ms adds on the last map alone at batch 64).
     def deconv(i, f, chain=True):
         ct, bn = model.deconv_layers[3 * i], model.deconv_layers[3 * i + 1]
         assert ct.bias is None
-        if chain and CHAIN_GRADS:
+        if chain:
             return DeconvBNReLUFn.apply(f, ct.weight, bn.weight, bn.bias, bn, dt, True)            # (y, f handed on)
         return DeconvBNReLUFn.apply(f, ct.weight, bn.weight, bn.bias, bn, dt), f
 
     def tz_head(fm, tail=None):
         if not tz_grad:
             return tz_head_train(model, fm.detach(), tail_stream=tail), fm
-        return tz_head_train(model, fm, True, tail_stream=tail) if CHAIN_GRADS else (tz_head_train(model, fm, tail_stream=tail), fm)
+        return tz_head_train(model, fm, True, tail_stream=tail)
 
     def dp_head(fm):                                                                   # whmr.py:656-658
-        return dp_head_train(model, fm, True) if CHAIN_GRADS else (dp_head_train(model, fm), fm)
+        return dp_head_train(model, fm, True)
 
     # Stage i of the regressor loop only reads feature map i, and the Tz head only enters the stages' projections (whmr.py:142-173), not the
     # next stage's input: after the first deconv stage the HEAVY chain (deconv 2, deconv 3, Tz head, IUV head: a few large launches) runs on a
@@ -294,7 +291,7 @@ def whmr_forward_train(model, x, center, scale, bbox_height, orig_shape, bbox_in
         # records and MapForkFn's backward adds them to the heads' gradient in place (maf_autograd.MapForkFn; WHMR_TRAIN_FORK3=0: plain fan-out)
         sink3 = None
         fm_last = fmaps[-1]
-        if FORK_SAMPLER3 and not (CHAIN_GRADS and CHAIN_SAMPLER3) and fm_last.requires_grad:
+        if FORK_SAMPLER3 and fm_last.requires_grad:
             sink3 = {}
             fmaps[-1], fm_last = MapForkFn.apply(fm_last, sink3)
         Tz, fm_heads = tz_head(fm_last, tail)
@@ -302,10 +299,8 @@ def whmr_forward_train(model, x, center, scale, bbox_height, orig_shape, bbox_in
             tz_ready = torch.cuda.Event()
             tz_ready.record(tail if tail is not None else heavy)
         if aux:
-            d, fm_heads = dp_head(fm_heads)
+            d, _ = dp_head(fm_heads)
             dp_out = [d]
-        if CHAIN_GRADS and CHAIN_SAMPLER3:
-            fmaps[-1] = fm_heads
     if heavy is not None and HEAVY_FIRST and not capturing:
         _backward_first([Tz, fmaps[1], fmaps[2]] + [d.nhwc for d in dp_out], [f_first])
     for i in range(3):
