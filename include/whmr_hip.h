@@ -411,6 +411,23 @@ int whmr_tz_unfold(const float* dtok, void* dP, int B, int OHp, int OWp, int OH,
 int whmr_estimate_translation(const float* S, const float* joints_2d, int B, int J, int j0, int nj, float focal, float img_w,
                               float img_h, float* out, void* stream);
 
+/* ---- evaluation metrics (csrc/pose_eval.hip).  Arithmetic after the fp32 loads is fp64; no atomics (repeated runs are bit-identical);
+ * nothing is allocated (graph-capturable).
+ * whmr_similarity_transform: compute_similarity_transform / reconstruction_error (utils/pose_utils.py:10-76, 3-D points only) for B samples at once:
+ *   S1, S2 [B, N, 3] fp32, N <= 64; S1_hat (nullable) [B, N, 3] = s R S1 + t, the proper similarity transform closest to S2; err (nullable) [B] =
+ *   mean over the N points of |S1_hat - S2|.  var1 = 0 (all S1 points equal) gives NaN, as numpy does.
+ * whmr_pose_metrics: the per-batch body of evaluate/eval.py:193-228 (also core/trainer.py:754-907) fused: pred_verts / gt_verts [B, V, 3] fp32,
+ *   J_reg [nJ, V] fp32 dense regressor (J_regressor_h36m: 17 x 6890), joint_map int32[nj] (H36M_TO_J14 / H36M_TO_J17, 1 <= nj <= 63).  Joints of
+ *   both meshes = J_reg . verts; pelvis = regressed row 0 (before the mapping); the joint_map rows minus the pelvis -> mpjpe [B], Procrustes -> pa_mpjpe
+ *   [B]; pve [B] = mean |pred - gt| over the raw vertices.  Metres in, metres out.  pred_j / pred_j_pa (nullable) [B, nj, 3]: the mapped,
+ *   pelvis-relative predicted joints before / after the alignment (eval.py's save_results 'pred' / 'pred_pa').  A map entry outside [0, nJ) gives NaN.
+ *   workspace: >= the bytes whmr_pose_metrics_workspace(B, V, nj) reports (fp64 per-chunk partials, fully rewritten by every call). */
+int whmr_similarity_transform(const float* S1, const float* S2, int B, int N, float* S1_hat, float* err, void* stream);
+int whmr_pose_metrics_workspace(int B, int V, int nj, long* bytes);
+int whmr_pose_metrics(const float* pred_verts, const float* gt_verts, int B, int V, const float* J_reg, int nJ, const int* joint_map, int nj,
+                      float* mpjpe, float* pa_mpjpe, float* pve, float* pred_j, float* pred_j_pa, void* workspace, long workspace_bytes,
+                      void* stream);
+
 /* Tz-head tail (whmr.py:574-577): tokens [B,T,D] -> mean over T -> Linear(D,Hd) -> Linear(Hd,1) -> BatchNorm1d(1) eval
  * (bn4 = weight, bias, running_mean, running_var) -> sigmoid -> x10. */
 int whmr_tz_tail(const float* tok, int B, int T, int D, const float* w0, const float* b0, int Hd, const float* w1,

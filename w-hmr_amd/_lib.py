@@ -142,6 +142,9 @@ _SIGS = {
     'whmr_debug_pkfma_canary': [_I, _I, _P, _P],
     'whmr_debug_mfma32_stream': [_I, _I, _P, _P],
     'whmr_estimate_translation': [_P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P],
+    'whmr_similarity_transform': [_P, _P, _I, _I, _P, _P, _P],
+    'whmr_pose_metrics_workspace': [_I, _I, _I, C.POINTER(C.c_long)],
+    'whmr_pose_metrics': [_P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P],
     'whmr_transpose_cast': [_P, _I, _L, _P, _I, _L, _I, _I, _I, _P],
     'whmr_colsum': [_P, _I, _L, _I, _I, _P, _I, _P, _P],
     'whmr_transpose_colsum': [_P, _L, _P, _L, _I, _I, _I, _P, _I, _P, _P],
@@ -1377,6 +1380,58 @@ def estimate_translation(S, joints_2d, j0, nj, focal, img_w, img_h):
     _check(lib().whmr_estimate_translation(S.data_ptr(), joints_2d.data_ptr(), B, J, j0, nj, focal, img_w, img_h, out.data_ptr(), _stream()),
            'whmr_estimate_translation')
     return out
+
+
+# ---- evaluation metrics (pose_eval.hip) -------------------------------------------------------------------------------
+def similarity_transform(S1, S2, S1_hat=None, err=None):
+    """Procrustes of every sample (utils/pose_utils.py:10-76): S1, S2 [B, N, 3] fp32 (N <= 64) -> (S1_hat [B, N, 3], err [B])."""
+    _dev(S1, S2, S1_hat, err)
+    S1, S2 = _f32c(S1), _f32c(S2)
+    assert S1.dim() == 3 and S1.shape[-1] == 3 and S2.shape == S1.shape, (S1.shape, S2.shape)
+    B, N = S1.shape[:2]
+    if S1_hat is None:
+        S1_hat = torch.empty_like(S1)
+    if err is None:
+        err = torch.empty(B, dtype=torch.float32, device=S1.device)
+    assert _f32c(S1_hat).shape == S1.shape and _f32c(err).shape == (B,)
+    _check(lib().whmr_similarity_transform(S1.data_ptr(), S2.data_ptr(), B, N, S1_hat.data_ptr(), err.data_ptr(), _stream()),
+           'whmr_similarity_transform')
+    return S1_hat, err
+
+
+def pose_metrics_workspace_bytes(B, V, nj):
+    n = C.c_long()
+    _check(lib().whmr_pose_metrics_workspace(B, V, nj, C.byref(n)), 'whmr_pose_metrics_workspace')
+    return n.value
+
+
+def pose_metrics(pred_verts, gt_verts, J_reg, joint_map, mpjpe=None, pa_mpjpe=None, pve=None, pred_j=None, pred_j_pa=None, workspace=None):
+    """evaluate/eval.py:193-228 for one batch: vertices [B, V, 3] fp32, J_reg [nJ, V] fp32, joint_map int32[nj] (device) -> per-sample
+    (mpjpe, pa_mpjpe, pve) [B] fp32 in the input's units.  pred_j / pred_j_pa: optional [B, nj, 3] outputs.  workspace: a uint8 device buffer of at
+    least pose_metrics_workspace_bytes(B, V, nj) bytes; allocated here when not given (pass one in to capture the call into a graph)."""
+    _dev(pred_verts, gt_verts, J_reg, joint_map, mpjpe, pa_mpjpe, pve, pred_j, pred_j_pa, workspace)
+    pred_verts, gt_verts, J_reg = _f32c(pred_verts), _f32c(gt_verts), _f32c(J_reg)
+    assert pred_verts.dim() == 3 and pred_verts.shape[-1] == 3 and gt_verts.shape == pred_verts.shape, (pred_verts.shape, gt_verts.shape)
+    B, V = pred_verts.shape[:2]
+    assert J_reg.dim() == 2 and J_reg.shape[1] == V, (J_reg.shape, V)
+    assert joint_map.dtype == torch.int32 and joint_map.dim() == 1 and joint_map.is_contiguous()
+    nj = joint_map.shape[0]
+    outs = []
+    for t in (mpjpe, pa_mpjpe, pve):
+        if t is None:
+            t = torch.empty(B, dtype=torch.float32, device=pred_verts.device)
+        assert _f32c(t).shape == (B,)
+        outs.append(t)
+    for t in (pred_j, pred_j_pa):
+        assert t is None or _f32c(t).shape == (B, nj, 3)
+    need = pose_metrics_workspace_bytes(B, V, nj)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=pred_verts.device)
+    assert workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need
+    _check(lib().whmr_pose_metrics(pred_verts.data_ptr(), gt_verts.data_ptr(), B, V, J_reg.data_ptr(), J_reg.shape[0], joint_map.data_ptr(), nj,
+                                   outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), _ptr(pred_j), _ptr(pred_j_pa), workspace.data_ptr(),
+                                   workspace.numel() * workspace.element_size(), _stream()), 'whmr_pose_metrics')
+    return tuple(outs)
 
 
 # ---- training mode of the deconv pyramid (deconv_train.hip) ----------------------------------------------------------

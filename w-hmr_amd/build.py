@@ -21,7 +21,8 @@ def _stale(target, deps):
 # contain the form are nevertheless built without packed-fp32 instructions -- they are memory- or latency-bound VALU kernels that run beside the GEMM
 # streams (the host pass prints "not a recognized feature" for the flag and ignores it).
 _NO_PK = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
-NO_PACKED_FP32 = {f: _NO_PK for f in ('smpl_lbs.hip', 'smpl_fused.hip', 'geometry.hip', 'iuv_loss.hip', 'maf_sampler.hip', 'rasterize.hip', 'vit_ops.hip')}
+NO_PACKED_FP32 = {f: _NO_PK for f in ('smpl_lbs.hip', 'smpl_fused.hip', 'geometry.hip', 'iuv_loss.hip', 'maf_sampler.hip', 'rasterize.hip', 'vit_ops.hip',
+                                         'pose_eval.hip')}
 if os.environ.get('WHMR_BUILD_PACKED_FP32', '0') == '1':                 # A/B
     NO_PACKED_FP32 = {}
 
