@@ -1,6 +1,7 @@
 """Backward pass of the ViT backbone (HIP GEMM / LayerNorm / GELU kernels) against the CPU oracle's autograd."""
 import math
 import os
+import sys
 
 import pytest
 import torch
@@ -119,31 +120,118 @@ def test_default_numerics_model_trains_in_fp32(dev):
         assert torch.equal(grads['bf16x3'][k], g), k
 
 
-@pytest.mark.parametrize('N', [196, 192, 100])
+def _bf16_reference():
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import bf16_reference
+    return bf16_reference
+
+
+def _attention_vs_float64(dev, B, N, H, qkv, dout, with_bwd):
+    """derived-bound check (tests/bf16_reference.py) of attention_fwd_train (o, lse) and of attention_bwd, fed both its own lse and the float64
+    one rounded to fp32 -> worst error / allowance"""
+    from whmr_amd import _lib as L
+    R = _bf16_reference()
+    d, scale = 64, 64 ** -0.5
+    qd = qkv.to(dev)
+    out = torch.empty(B * N, H * d, dtype=torch.bfloat16, device=dev)
+    lse = torch.empty(B * H * N, device=dev)
+    L.attention_fwd_train(qd, out, lse, B, N, H, d, scale)
+    (ro, mo), (rl, ml) = R.attention_fwd(qd, B, N, H, d, scale)
+    worst = {'o': R.check(out, ro, mo, n_round=R.N_ROUND_ATT_FWD), 'lse': R.check(lse, rl, ml)}
+    if with_bwd:
+        dd = dout.to(dev)
+        nr = R.attention_bwd_n_round(B, N, H, d, dev)
+        for tag, ls in (('own lse', lse), ('float64 lse', rl.float())):
+            dqkv = torch.empty_like(qd)
+            L.attention_bwd(qd, out, dd, ls, dqkv, B, N, H, d, scale)
+            r, m = R.attention_bwd(qd, out, dd, ls, B, N, H, d, scale)
+            worst['dqkv, ' + tag] = R.check(dqkv, r, m, n_round=nr)
+    bad = {k: v for k, v in worst.items() if not v <= 1.0}
+    assert not bad, 'attention (B %d, N %d, H %d) exceeds its derived bound: %s' % (B, N, H, bad)
+    print('attention B %d N %d H %d: %s' % (B, N, H, ', '.join('%s %.2e' % kv for kv in worst.items())))
+
+
+# every NKT instance of the forward (3..8) and of the backward (3..7), ragged and full last key tiles, a last tile with one real key (97, 129, 225)
+@pytest.mark.parametrize('N', [196, 192, 100, 65, 96, 97, 128, 129, 160, 224, 225, 256])
 def test_attention_backward_kernel(dev, N):
-    """MFMA attention backward vs autograd of the fp32 attention on the same bf16 inputs."""
+    """MFMA attention backward vs autograd of the fp32 attention on the same bf16 inputs; then forward and backward against float64 with the
+    bound derived from their roundings, at the batch x heads of the training step too (64 x 12 ViT-B, 32 x 16 ViT-L) and with peaked logits."""
     from whmr_amd import _lib as L
     B, H, d = 2, 3, 64
     g = torch.Generator().manual_seed(N)
     qkv = (torch.randn(B, N, 3, H, d, generator=g) * 1.5).bfloat16()
     dout = torch.randn(B, N, H * d, generator=g)
     scale = d ** -0.5
-    ref_in = qkv.float().requires_grad_(True)
-    q, k, v = ref_in.permute(2, 0, 3, 1, 4)
-    o_ref = (torch.softmax((q * scale) @ k.transpose(-1, -2), -1) @ v).transpose(1, 2).reshape(B, N, H * d)
-    o_ref.backward(dout)
-    qd = qkv.view(B * N, 3 * H * d).to(dev)
-    out = torch.empty(B * N, H * d, dtype=torch.bfloat16, device=dev)
-    lse = torch.empty(B * H * N, device=dev)
-    L.attention_fwd_train(qd, out, lse, B, N, H, d, scale)
-    assert _rel(out.float().cpu().view(B, N, -1), o_ref.detach()) < 2e-2
-    lse_ref = torch.logsumexp((q * scale) @ k.transpose(-1, -2), -1).detach() / math.log(2.0)          # [B, H, N], log2 domain
-    assert (lse.cpu().view(B, H, N) - lse_ref).abs().max() < 2e-2
-    dqkv = torch.empty_like(qd)
-    L.attention_bwd(qd, out, dout.view(B * N, -1).contiguous().to(dev), lse, dqkv, B, N, H, d, scale)
-    got = dqkv.float().cpu().view(B, N, 3, H, d)
-    for i, name in enumerate('qkv'):
-        assert _rel(got[:, :, i], ref_in.grad[:, :, i]) < 3e-2, name
+    with_bwd = N <= 224                                                                 # the backward kernel's envelope: 64 < N <= 224
+    if with_bwd:
+        ref_in = qkv.float().requires_grad_(True)
+        q, k, v = ref_in.permute(2, 0, 3, 1, 4)
+        o_ref = (torch.softmax((q * scale) @ k.transpose(-1, -2), -1) @ v).transpose(1, 2).reshape(B, N, H * d)
+        o_ref.backward(dout)
+        qd = qkv.view(B * N, 3 * H * d).to(dev)
+        out = torch.empty(B * N, H * d, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(B * H * N, device=dev)
+        L.attention_fwd_train(qd, out, lse, B, N, H, d, scale)
+        assert _rel(out.float().cpu().view(B, N, -1), o_ref.detach()) < 2e-2
+        lse_ref = torch.logsumexp((q * scale) @ k.transpose(-1, -2), -1).detach() / math.log(2.0)          # [B, H, N], log2 domain
+        assert (lse.cpu().view(B, H, N) - lse_ref).abs().max() < 2e-2
+        dqkv = torch.empty_like(qd)
+        L.attention_bwd(qd, out, dout.view(B * N, -1).contiguous().to(dev), lse, dqkv, B, N, H, d, scale)
+        got = dqkv.float().cpu().view(B, N, 3, H, d)
+        for i, name in enumerate('qkv'):
+            assert _rel(got[:, :, i], ref_in.grad[:, :, i]) < 3e-2, name
+    cases = [(B, H, qkv.view(B * N, 3 * H * d), dout.view(B * N, H * d))]
+    if N in (129, 196):                                                                 # peaked attention: logits up to ~ +-30 (exp2 / lse range)
+        qp = torch.randn(B * N, 3 * H * d, generator=g) * 2.6
+        cases.append((B, H, qp.bfloat16(), torch.randn(B * N, H * d, generator=g)))
+    for Bb, Hb in {192: [(64, 12), (32, 16)], 196: [(64, 12)]}.get(N, []):
+        cases.append((Bb, Hb, (torch.randn(Bb * N, 3 * Hb * d, generator=g) * 1.5).bfloat16(), torch.randn(Bb * N, Hb * d, generator=g)))
+    for Bb, Hb, qx, dx in cases:
+        _attention_vs_float64(dev, Bb, N, Hb, qx, dx, with_bwd)
+
+
+@pytest.mark.parametrize('C', [216, 768, 772, 1024])
+def test_layernorm_bwd_kernel_vs_float64(dev, C):
+    """whmr_layernorm_bwd against float64 with the fp32 bound, across the MAXV 3 / 4 instances (C <= 768 < C) and the launch switch at 4096
+    rows (one workgroup per 4 rows below, 1024 grid-striding workgroups and 1024 partials from 4096 up); dres absent / separate / aliased to dx,
+    accumulate onto prefilled dgamma / dbeta, cast_out with and without a row_scale holding zeros; rows with a +30 mean and an outlier channel."""
+    from whmr_amd import _lib as L
+    R = _bf16_reference()
+    g = torch.Generator().manual_seed(C)
+    worst = {}
+
+    def rec(key, v):
+        assert v <= 1.0, (C, key, v)
+        worst[key] = max(worst.get(key, 0.0), v)
+
+    for rows in (1, 50, 4095, 4096, 4097, 12288):
+        for mode in ('none', 'separate', 'alias'):
+            x = torch.randn(rows, C, generator=g)
+            if mode == 'alias':                                                         # large row mean and one outlier channel
+                x = x + 30.0
+                x[:, 7] = x[:, 7] * 8.0
+            x, dy = x.to(dev), torch.randn(rows, C, generator=g).to(dev)
+            gam = (torch.randn(C, generator=g) * 0.5 + 1.0).to(dev)
+            dres = torch.randn(rows, C, generator=g).to(dev) if mode != 'none' else None
+            acc = mode == 'separate'
+            dg0, db0 = torch.randn(C, generator=g).to(dev), torch.randn(C, generator=g).to(dev)
+            dg, db = dg0.clone(), db0.clone()
+            dx = dres.clone() if mode == 'alias' else torch.full((rows, C), float('nan'), device=dev)
+            rs = None
+            if mode != 'none':
+                rs = torch.tensor([0.0, 1 / 0.7, 1.0], device=dev).repeat(rows // 3 + 1)[:rows].contiguous()
+            cast = torch.empty(rows, C, dtype=torch.bfloat16, device=dev) if mode != 'none' or rows == 4097 else None
+            L.layernorm_bwd(x, dy, gam, dx if mode == 'alias' else dres, dx, dg, db, 1e-6, accumulate=acc, cast_out=cast,
+                            row_scale=rs if cast is not None else None)
+            ref = R.layernorm_bwd(x, dy, gam, 1e-6, dres=dres, dgamma_prior=dg0 if acc else None, dbeta_prior=db0 if acc else None)
+            rec('dx', R.check(dx, *ref['dx']))
+            rec('dgamma', R.check(dg, *ref['dgamma'], kappa=R.KAPPA_SUM))
+            rec('dbeta', R.check(db, *ref['dbeta'], kappa=R.KAPPA_SUM))
+            if cast is not None:
+                assert torch.equal(cast, R.cast_rows(dx, rs)), (C, rows, mode)
+                if rs is not None:
+                    assert not cast[0::3].any()
+    print('layernorm_bwd C %d: %s' % (C, ', '.join('%s %.2e' % kv for kv in worst.items())))
 
 
 def test_vit_backward_224_hip_attention(dev):
