@@ -577,6 +577,23 @@ int whmr_iuv_losses(const void* y, int y_bf16, long ld, const float* iuv, long s
 int whmr_iuv_losses_bwd(const void* y, int y_bf16, long ld, const float* iuv, long sb, long sc, long sh, long sw, int B, int H, int W,
                         float point_weight, const float* g, void* dy, long ldg, void* stream);
 
+/* ---- output side of the demo: mesh overlay renderer (csrc/mesh_render.hip) = render_overlay_image (utils/renderer_cam.py:41-141: pyrender scene,
+ * IntrinsicsCamera, OffscreenRenderer, valid-mask composite) as render_image_group (:144-225) calls it per person from demo/tester.py:176-214.
+ * verts [P, V, 3] fp32; faces [F, 3] int32 (indices in [0, V): the caller checks); vf_ptr [V + 1] / vf_idx [3 F] int32: vertex -> face CSR of the
+ * smooth normals; cam_t [P, 3], focal [P, 2] = (fx, fy) on the device; (cx, cy) camera centre; rot: 9 HOST floats (camera_rotation, row-major) or
+ * null = identity; side_cos / side_sin of sideview_angle; a face with a vertex at depth <= znear is dropped; frame [H, W, 3] uint8 or null (black
+ * background); per_person 0: all persons in ONE image (shared depth buffer), 1: one image per person (NI = per_person ? P : 1).
+ * rgb = clamp(base * (ambient + k_d * max(n . l, 0)), 0, 1), (lx, ly, lz) the unit direction TO the light in pyrender's world frame (the shader is
+ * defined by this library: see the kernel file).  Scratch: scr, nrm [P, V, 3] fp32 (scr holds (u, v, depth) of every vertex on return), zbuf
+ * [NI, H, W] uint64.  out [NI, H, W, 3] uint8 (background = frame); optional, or null: color_out [NI, H, W, 3] fp32, face_out [NI, H, W] int32 (global
+ * face id person * F + face, -1 = background), depth_out [NI, H, W] fp32 (0 = background).  Three launches, no allocation, no synchronisation;
+ * bit-reproducible. */
+int whmr_mesh_render(const float* verts, int P, int V, const int32_t* faces, int F, const int32_t* vf_ptr, const int32_t* vf_idx,
+                     const float* cam_t, const float* focal, float cx, float cy, const float* rot, float side_cos, float side_sin, float znear,
+                     const uint8_t* frame, int H, int W, int per_person, float base_r, float base_g, float base_b, float ambient, float k_d,
+                     float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, uint8_t* out, float* color_out, int32_t* face_out,
+                     float* depth_out, void* stream);
+
 /* ---- attainable ceilings of the box the benchmark runs on (csrc/ceilings.hip; SURVEY 8(d) "datasheet numbers AND measure on the box"); replaces no
  * reference code -- bench.py calls them after its timed region and reports them as roofline.attainable / sclk_mhz_observed.
  * whmr_mfma_ceiling: `blocks` workgroups x 4 waves, each `iters` x 8 register-fed v_mfma_f32_16x16x32_bf16 on random operands

@@ -4,6 +4,7 @@ PyTorch is used only for device memory and the current HIP stream.  There is NO 
 library is missing, or a tensor is not on a HIP device, these functions raise.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -174,6 +175,8 @@ _SIGS = {
     'whmr_attention_bwd_f32': [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     'whmr_scale_rows_cast': [_P, _P, _P, _I, _I, _I, _P],
     'whmr_iuv_rasterize': [_P, _I, _I, _P, _I, _P, _I, _P, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    'whmr_mesh_render': [_P, _I, _I, _P, _I, _P, _P, _P, _P, _F, _F, _P, _F, _F, _F, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
+                         _P, _P],
     'whmr_iuv_losses': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     'whmr_iuv_losses_bwd': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _L, _P],
     'whmr_weights_prepare': [_P, _I, _I, _P],
@@ -720,6 +723,72 @@ def iuv_rasterize(verts, faces, tex, cam, K, focal, orig_size, out_size, vmap=No
                                     K[0], K[1], K[2], K[3], focal, orig_size[0], orig_size[1], H, W, scr.data_ptr(), zbuf.data_ptr(), out.data_ptr(),
                                     _ptr(fo), _stream()), 'whmr_iuv_rasterize')
     return (out, fo) if want_faces else out
+
+
+_mesh_ws = {}
+
+
+def mesh_render(verts, faces, vf_ptr, vf_idx, cam_t, focal, center, frame, size, color, rot=None, sideview_angle=0.0, per_person=False, znear=0.05,
+                ambient=0.3, k_d=4 * (1 - 0.2) * (1 - 0.04) / math.pi, light=(0.0, 0.0, 1.0), want=()):
+    """Mesh overlay image(s) of ``verts`` [P, V, 3] over ``frame`` [H, W, 3] uint8 or None = black (include/whmr_hip.h: whmr_mesh_render).  faces
+    [F, 3] / vf_ptr [V + 1] / vf_idx [3 F] int32 (the caller has checked the indices against V); cam_t [P, 3], focal [P, 2] fp32 on the device; center
+    (cx, cy), size (H, W), color (r, g, b) in 0..1; rot: 3 x 3 HOST values or None.  Returns uint8 [H, W, 3] ([P, H, W, 3] with per_person), or a dict
+    with 'image' and the entries asked for in ``want``: 'color' fp32, 'face' int32 global face id (-1 = background), 'depth' fp32, 'screen' [P, V, 3] =
+    (u, v, depth) of every vertex.  The scratch (screen vertices, normals, z-buffer) is cached per (device, stream, shape); outputs are fresh."""
+    _dev(verts, faces, vf_ptr, vf_idx, cam_t, focal, frame)
+    verts, cam_t, focal = _f32c(verts), _f32c(cam_t), _f32c(focal)
+    P, V = verts.shape[0], verts.shape[1]
+    F = faces.shape[0]
+    H, W = int(size[0]), int(size[1])
+    assert verts.dim() == 3 and verts.shape[2] == 3 and tuple(cam_t.shape) == (P, 3) and tuple(focal.shape) == (P, 2)
+    assert faces.dtype == torch.int32 and faces.is_contiguous() and faces.dim() == 2 and faces.shape[1] == 3
+    assert vf_ptr.dtype == torch.int32 and vf_ptr.is_contiguous() and vf_ptr.numel() == V + 1
+    assert vf_idx.dtype == torch.int32 and vf_idx.is_contiguous() and vf_idx.numel() == 3 * F
+    assert P >= 1 and H >= 1 and W >= 1 and P * F < 2 ** 31
+    if frame is not None:
+        assert frame.dtype == torch.uint8 and frame.is_contiguous() and tuple(frame.shape) == (H, W, 3)
+    unknown = set(want) - {'color', 'face', 'depth', 'screen'}
+    assert not unknown, 'unknown outputs %s' % sorted(unknown)
+    dev = verts.device
+    NI = P if per_person else 1
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream, P, V, NI, H, W)
+    ws = _mesh_ws.get(key)
+    if ws is None:
+        if len(_mesh_ws) >= 8:                                           # a few (person count, frame size) pairs at a time, not every one ever seen
+            _mesh_ws.pop(next(iter(_mesh_ws)))
+        ws = _mesh_ws[key] = (torch.empty(P, V, 3, dtype=torch.float32, device=dev), torch.empty(P, V, 3, dtype=torch.float32, device=dev),
+                              torch.empty(NI, H, W, dtype=torch.int64, device=dev))
+    scr, nrm, zbuf = ws
+    out = torch.empty(NI, H, W, 3, dtype=torch.uint8, device=dev)
+    col = torch.empty(NI, H, W, 3, dtype=torch.float32, device=dev) if 'color' in want else None
+    fid = torch.empty(NI, H, W, dtype=torch.int32, device=dev) if 'face' in want else None
+    dep = torch.empty(NI, H, W, dtype=torch.float32, device=dev) if 'depth' in want else None
+    rot_c = None
+    if rot is not None:
+        r = [float(v) for row in rot for v in row]
+        assert len(r) == 9
+        rot_c = (C.c_float * 9)(*r)
+    a = math.radians(float(sideview_angle))
+    lx, ly, lz = (float(v) for v in light)
+    _check(lib().whmr_mesh_render(verts.data_ptr(), P, V, faces.data_ptr(), F, vf_ptr.data_ptr(), vf_idx.data_ptr(), cam_t.data_ptr(), focal.data_ptr(),
+                                  float(center[0]), float(center[1]), C.cast(rot_c, C.c_void_p) if rot_c is not None else None, math.cos(a), math.sin(a),
+                                  float(znear), _ptr(frame), H, W, int(bool(per_person)), float(color[0]), float(color[1]), float(color[2]),
+                                  float(ambient), float(k_d), lx, ly, lz, scr.data_ptr(), nrm.data_ptr(), zbuf.data_ptr(), out.data_ptr(), _ptr(col),
+                                  _ptr(fid), _ptr(dep), _stream()), 'whmr_mesh_render')
+    img = out if per_person else out[0]
+    if not want:
+        return img
+    sq = (lambda t: t) if per_person else (lambda t: t[0])
+    res = {'image': img}
+    if col is not None:
+        res['color'] = sq(col)
+    if fid is not None:
+        res['face'] = sq(fid)
+    if dep is not None:
+        res['depth'] = sq(dep)
+    if 'screen' in want:
+        res['screen'] = scr.clone()
+    return res
 
 
 def _iuv_loss_args(y, iuv):

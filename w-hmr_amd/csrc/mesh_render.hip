@@ -1,0 +1,268 @@
+// Mesh overlay renderer of the demo (replaces utils/renderer_cam.py:41-141 render_overlay_image -- pyrender on an OpenGL / EGL context -- as
+// demo/tester.py:176-214 drives it through render_image_group): all persons of a frame drawn over the uint8 frame, on the device, in three launches.
+// pyrender and trimesh are third-party and absent from the reference tree, so the scene is restated from the call site and the shader is DEFINED here.
+//
+// Camera (renderer_cam.py:71-114).  With t' = (-t_x, t_y, t_z) (``camera_translation[0] *= -1``), D = diag(1, -1, -1) (the 180 degree turn about X),
+// S = R_y(sideview_angle) and the camera pose [R | R t'], a mesh vertex p stands at  q = S D p  in the world and at  p_c = R^T q - t'  in the camera's
+// frame.  IntrinsicsCamera(fx, fy, cx, cy) looks down -z with y up: from its projection matrix a point lands at  u = cx + fx x_c / (-z_c),
+// v = cy - fy y_c / (-z_c)  (v counted from the top row) with depth -z_c.  In the computer-vision frame  (X, Y, Z) = D p_c = D R^T S D p + (t_x, t_y, t_z):
+//     u = cx + fx X / Z,    v = cy + fy Y / Z,    depth Z,    pixel (j, i) samples its centre (i + 0.5, j + 0.5).
+// R = I, no side view:  u = cx + fx (x + t_x) / (z + t_z),  v = cy + fy (y + t_y) / (z + t_z),  depth z + t_z -- perspective_projection (geometry.hip).
+//
+// Normals: smooth per-vertex normals, the sum of (v1 - v0) x (v2 - v0) (= 2 area x unit normal: area weighting) over the faces around a vertex,
+// normalised.  The sum walks a vertex -> face CSR in its stored order: no float atomics, the same bits every run.  trimesh's own weighting (it
+// blends by corner angle in some versions) is unpinned.  The normal is kept in the WORLD frame, n_w = S D n, where the lights are.
+//
+// Coverage: top-left fill rule.  Every edge function is evaluated from the edge's lexicographically smaller end point whatever face asks, and negated
+// for the face that walks the edge the other way (exact in floating point), so the two faces of a shared edge see the same number with opposite signs:
+// a pixel centre exactly on the edge goes to exactly one of them (the one for which it is a left edge, or a top edge if horizontal).  Both windings
+// render.  A face with any vertex at depth <= znear (pyrender's IntrinsicsCamera default 0.05, from memory, unverified: a parameter), a NaN vertex or
+// an empty pixel box is dropped whole.  z-buffer key = depth bits << 32 | global face id (person * F + face), 64-bit atomic min: nearest face, ties to
+// the smaller id, bit-reproducible (as rasterize.hip).  The IUV kernel's strict-interior rule is pytorch3d's and stays there.
+//
+// Shading (DEFINED here, a stated deviation):  rgb = clamp(base * (ambient + k_d * max(n . l, 0)), 0, 1).  Every light of renderer_cam.py:116-128 is a
+// DirectionalLight whose pose sets a translation only -- a directional light ignores it -- so all four shine along world -z: l = (0, 0, 1) is the
+// direction TO the light, k_d = n_lights (1 - metallic) (1 - 0.04) / pi with metallic 0.2, n_lights 4: the diffuse term of the glTF metallic-roughness
+// model.  The specular lobe (default roughness 1.0) is left out.  alphaMode 'OPAQUE': alpha does nothing in the reference and is no parameter.
+// Background pixels keep the frame's bytes (the valid mask of :138-140, not a blend); uint8 = round-half-even(255 * rgb) of the fp32 colour.
+#include "common.h"
+
+struct mesh_cam { float cx, cy, sc, ss; int has_rot; float r[9]; };
+
+// Launch 1: z-buffer clear + one thread per (person, vertex): camera transform, projection, vertex normal.
+__global__ __launch_bounds__(256) void mesh_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, const int32_t* __restrict__ vf_ptr,
+                                                          const int32_t* __restrict__ vf_idx, const float* __restrict__ cam_t, const float* __restrict__ focal,
+                                                          float* __restrict__ scr, float* __restrict__ nrm, unsigned long long* __restrict__ zbuf, long npix,
+                                                          int P, int V, mesh_cam c) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < npix) zbuf[idx] = ~0ull;
+    if (idx >= (long)P * V) return;
+    const int p = (int)(idx / V), v = (int)(idx - (long)p * V);
+    const float* vp = verts + (size_t)p * V * 3;
+    // world: q = S D p,  S = [[c, 0, s], [0, 1, 0], [-s, 0, c]]
+    const float x = vp[v * 3], y = -vp[v * 3 + 1], z = -vp[v * 3 + 2];
+    const float qx = c.sc * x + c.ss * z, qy = y, qz = c.sc * z - c.ss * x;
+    float px = qx, py = qy, pz = qz;
+    if (c.has_rot) {                                                              // p_c = R^T q
+        px = (c.r[0] * qx + c.r[3] * qy) + c.r[6] * qz;
+        py = (c.r[1] * qx + c.r[4] * qy) + c.r[7] * qz;
+        pz = (c.r[2] * qx + c.r[5] * qy) + c.r[8] * qz;
+    }
+    const float X = px + cam_t[p * 3], Y = cam_t[p * 3 + 1] - py, Z = cam_t[p * 3 + 2] - pz;
+    scr[idx * 3] = c.cx + focal[p * 2] * X / Z;
+    scr[idx * 3 + 1] = c.cy + focal[p * 2 + 1] * Y / Z;
+    scr[idx * 3 + 2] = Z;
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    for (int k = vf_ptr[v]; k < vf_ptr[v + 1]; ++k) {
+        const int32_t* f = faces + (size_t)vf_idx[k] * 3;
+        const float* a = vp + (size_t)f[0] * 3;
+        const float* b = vp + (size_t)f[1] * 3;
+        const float* d = vp + (size_t)f[2] * 3;
+        const float e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2], e2x = d[0] - a[0], e2y = d[1] - a[1], e2z = d[2] - a[2];
+        nx += e1y * e2z - e1z * e2y; ny += e1z * e2x - e1x * e2z; nz += e1x * e2y - e1y * e2x;
+    }
+    const float inv = __builtin_amdgcn_rsqf(fmaxf((nx * nx + ny * ny) + nz * nz, 1e-30f));
+    nx *= inv; ny = -ny * inv; nz = -nz * inv;                                    // D n
+    nrm[idx * 3] = c.sc * nx + c.ss * nz; nrm[idx * 3 + 1] = ny; nrm[idx * 3 + 2] = c.sc * nz - c.ss * nx;
+}
+
+// Edge function of the oriented edge a -> b at p, evaluated from the lexicographically smaller end point (see the header): the explicit fma keeps
+// the rounding the same at every call site.
+__device__ __forceinline__ float mesh_edge(float ax, float ay, float bx, float by, float px, float py) {
+    const bool sw = bx < ax || (bx == ax && by < ay);
+    const float lx = sw ? bx : ax, ly = sw ? by : ay, hx = sw ? ax : bx, hy = sw ? ay : by;
+    const float e = __fmaf_rn(px - lx, hy - ly, -((py - ly) * (hx - lx)));
+    return sw ? -e : e;
+}
+// a -> b is a left edge (the interior, e > 0, lies towards +x) or a top edge (horizontal, interior towards +y: rows grow downwards)
+__device__ __forceinline__ bool mesh_top_left(float ax, float ay, float bx, float by) { return by > ay || (by == ay && bx < ax); }
+
+// Per-face setup + per-pixel test, one code path for the z-buffer pass and the resolve pass: coverage and depth agree bit for bit between them.
+// The face is taken in the winding that makes its doubled area positive; tl_i: edge i (opposite vertex i) owns the centres lying exactly on it.
+struct mesh_tri { float v[9]; float area, ra, rz0, rz1, rz2; bool tl0, tl1, tl2; };
+__device__ __forceinline__ bool mesh_setup(mesh_tri& t) {
+    t.area = mesh_edge(t.v[0], t.v[1], t.v[3], t.v[4], t.v[6], t.v[7]);
+    t.ra = __builtin_amdgcn_rcpf(t.area);
+    t.rz0 = __builtin_amdgcn_rcpf(t.v[2]); t.rz1 = __builtin_amdgcn_rcpf(t.v[5]); t.rz2 = __builtin_amdgcn_rcpf(t.v[8]);
+    const bool pos = t.area > 0.f;
+    t.tl0 = pos ? mesh_top_left(t.v[3], t.v[4], t.v[6], t.v[7]) : mesh_top_left(t.v[6], t.v[7], t.v[3], t.v[4]);
+    t.tl1 = pos ? mesh_top_left(t.v[6], t.v[7], t.v[0], t.v[1]) : mesh_top_left(t.v[0], t.v[1], t.v[6], t.v[7]);
+    t.tl2 = pos ? mesh_top_left(t.v[0], t.v[1], t.v[3], t.v[4]) : mesh_top_left(t.v[3], t.v[4], t.v[0], t.v[1]);
+    return t.area != 0.f && t.area == t.area;
+}
+__device__ __forceinline__ bool mesh_bary(const mesh_tri& t, float px, float py, float& b0, float& b1, float& b2, float& pz) {
+    const float e0 = mesh_edge(t.v[3], t.v[4], t.v[6], t.v[7], px, py);
+    const float e1 = mesh_edge(t.v[6], t.v[7], t.v[0], t.v[1], px, py);
+    const float e2 = mesh_edge(t.v[0], t.v[1], t.v[3], t.v[4], px, py);
+    const float s0 = t.area > 0.f ? e0 : -e0, s1 = t.area > 0.f ? e1 : -e1, s2 = t.area > 0.f ? e2 : -e2;
+    const bool in = (s0 > 0.f || (s0 == 0.f && t.tl0)) && (s1 > 0.f || (s1 == 0.f && t.tl1)) && (s2 > 0.f || (s2 == 0.f && t.tl2));
+    if (!in) return false;
+    const float q0 = (e0 * t.ra) * t.rz0, q1 = (e1 * t.ra) * t.rz1, q2 = (e2 * t.ra) * t.rz2;      // perspective-correct: b_i ~ w_i / z_i
+    const float rden = __builtin_amdgcn_rcpf((q0 + q1) + q2);
+    b0 = q0 * rden; b1 = q1 * rden; b2 = q2 * rden;
+    pz = (b0 * t.v[2] + b1 * t.v[5]) + b2 * t.v[8];
+    return pz > 0.f;
+}
+
+// Launch 2: one lane per (person, face) finds the face's pixel box; boxes of at most MESH_SMALL pixels are walked by that lane, larger ones by the WHOLE
+// wave, 64 pixels at a time (the walk of rasterize.hip: a close-up person at frame resolution has faces of tens to thousands of pixels, a distant one
+// of one or two).  Same per-pixel arithmetic on both paths.
+#define MESH_SMALL 16
+__device__ __forceinline__ void mesh_pixel(const mesh_tri& t, int x, int y, unsigned gid, unsigned long long* __restrict__ z0, int W) {
+    float b0, b1, b2, pz;
+    if (!mesh_bary(t, x + 0.5f, y + 0.5f, b0, b1, b2, pz)) return;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(pz) << 32) | gid;
+    unsigned long long* z = z0 + (size_t)y * W + x;
+    // the z-buffer only ever decreases: a plain look first drops the faces that are already hidden (the far side of every closed mesh)
+    if (__hip_atomic_load(z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(z, key);
+}
+
+__global__ __launch_bounds__(256) void mesh_faces_kernel(const float* __restrict__ scr, const int32_t* __restrict__ faces, unsigned long long* __restrict__ zbuf,
+                                                         int P, int V, int F, int H, int W, int per_person, float znear) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    mesh_tri t;
+    int x0 = 0, x1 = -1, y0 = 0, y1 = -1, img = 0;
+    unsigned gid = 0;
+    bool ok = false;
+    if (idx < (long)P * F) {
+        const int p = (int)(idx / F), f = (int)(idx - (long)p * F);
+        gid = (unsigned)idx; img = per_person ? p : 0;
+        const float* s = scr + (size_t)p * V * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float* vp = s + (size_t)faces[f * 3 + k] * 3;
+            t.v[3 * k] = vp[0]; t.v[3 * k + 1] = vp[1]; t.v[3 * k + 2] = vp[2];
+        }
+        const float xmin = fminf(t.v[0], fminf(t.v[3], t.v[6])), xmax = fmaxf(t.v[0], fmaxf(t.v[3], t.v[6]));
+        const float ymin = fminf(t.v[1], fminf(t.v[4], t.v[7])), ymax = fmaxf(t.v[1], fmaxf(t.v[4], t.v[7]));
+        // every comparison is false for a NaN, but fminf / fmaxf skip one: the sum of the screen coordinates is looked at as well (inf - inf: dropped too)
+        const float any = ((t.v[0] + t.v[1]) + (t.v[3] + t.v[4])) + (t.v[6] + t.v[7]);
+        ok = t.v[2] > znear && t.v[5] > znear && t.v[8] > znear && any == any && xmax >= 0.5f && ymax >= 0.5f && xmin <= (float)W - 0.5f &&
+             ymin <= (float)H - 0.5f;
+        if (ok) {                                                                 // centres i + 0.5 in [min, max]; clamped as floats, so the casts are in range
+            x0 = (int)fmaxf(ceilf(xmin - 0.5f), 0.f); x1 = (int)fminf(floorf(xmax - 0.5f), (float)(W - 1));
+            y0 = (int)fmaxf(ceilf(ymin - 0.5f), 0.f); y1 = (int)fminf(floorf(ymax - 0.5f), (float)(H - 1));
+        }
+    }
+    if (!ok) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) t.v[k] = 1.f;
+    }
+    ok = mesh_setup(t) && ok;
+    const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
+    const int npx = (bw > 0 && bh > 0 && ok) ? bw * bh : 0;
+    if (npx > 0 && npx <= MESH_SMALL) {
+        unsigned long long* z0 = zbuf + (size_t)img * H * W;
+        for (int y = y0; y <= y1; ++y)
+            for (int x = x0; x <= x1; ++x) mesh_pixel(t, x, y, gid, z0, W);
+    }
+    unsigned long long big = __ballot(npx > MESH_SMALL);
+    while (big) {
+        const int L = __ffsll((long long)big) - 1;
+        big &= big - 1;
+        mesh_tri u;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) u.v[k] = __shfl(t.v[k], L, 64);
+        mesh_setup(u);                                                            // the same arithmetic on the same inputs: the owner lane's bits
+        const int ux0 = __shfl(x0, L, 64), uy0 = __shfl(y0, L, 64), ux1 = __shfl(x1, L, 64), uy1 = __shfl(y1, L, 64);
+        const unsigned ug = (unsigned)__shfl((int)gid, L, 64);
+        unsigned long long* z0 = zbuf + (size_t)__shfl(img, L, 64) * H * W;
+        // the box in 64-pixel tiles shaped after its height (64 x 1 ... 8 x 8), lane = pixel of the tile: no per-pixel index division
+        const int uh = uy1 - uy0 + 1;
+        const int lw = uh <= 1 ? 6 : uh <= 2 ? 5 : uh <= 4 ? 4 : 3;
+        const int tw = 1 << lw, th = 64 >> lw;
+        const int lx = lane & (tw - 1), ly = lane >> lw;
+        for (int ty = uy0; ty <= uy1; ty += th)
+            for (int tx = ux0; tx <= ux1; tx += tw) {
+                const int x = tx + lx, y = ty + ly;
+                if (x <= ux1 && y <= uy1) mesh_pixel(u, x, y, ug, z0, W);
+            }
+    }
+}
+
+struct mesh_shade { float r, g, b, ambient, kd, lx, ly, lz; };
+
+// Launch 3: one thread per pixel of every output image.
+__global__ __launch_bounds__(256) void mesh_resolve_kernel(const float* __restrict__ scr, const float* __restrict__ nrm, const int32_t* __restrict__ faces,
+                                                           const unsigned long long* __restrict__ zbuf, const uint8_t* __restrict__ frame,
+                                                           uint8_t* __restrict__ out, float* __restrict__ color_out, int32_t* __restrict__ face_out,
+                                                           float* __restrict__ depth_out, int NI, int V, int F, int H, int W, mesh_shade m) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long plane = (long)H * W;
+    if (idx >= NI * plane) return;
+    const long r = idx % plane;
+    const int y = (int)(r / W), x = (int)(r - (long)y * W);
+    const unsigned long long key = zbuf[idx];
+    int gid = -1;
+    float c0 = 0.f, c1 = 0.f, c2 = 0.f, depth = 0.f;
+    bool hit = false;
+    if (key != ~0ull) {
+        gid = (int)(key & 0xffffffffu);
+        const int p = gid / F, f = gid - p * F;
+        const float* s = scr + (size_t)p * V * 3;
+        const float* n = nrm + (size_t)p * V * 3;
+        const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+        mesh_tri t;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { t.v[k] = s[(size_t)i0 * 3 + k]; t.v[3 + k] = s[(size_t)i1 * 3 + k]; t.v[6 + k] = s[(size_t)i2 * 3 + k]; }
+        mesh_setup(t);
+        float b0, b1, b2;
+        hit = mesh_bary(t, x + 0.5f, y + 0.5f, b0, b1, b2, depth);                // true: the face pass took the same path
+        if (hit) {
+            const float nx = (b0 * n[(size_t)i0 * 3] + b1 * n[(size_t)i1 * 3]) + b2 * n[(size_t)i2 * 3];
+            const float ny = (b0 * n[(size_t)i0 * 3 + 1] + b1 * n[(size_t)i1 * 3 + 1]) + b2 * n[(size_t)i2 * 3 + 1];
+            const float nz = (b0 * n[(size_t)i0 * 3 + 2] + b1 * n[(size_t)i1 * 3 + 2]) + b2 * n[(size_t)i2 * 3 + 2];
+            const float inv = __builtin_amdgcn_rsqf(fmaxf((nx * nx + ny * ny) + nz * nz, 1e-30f));
+            const float ndl = fmaxf(((nx * m.lx + ny * m.ly) + nz * m.lz) * inv, 0.f);
+            const float lum = m.ambient + m.kd * ndl;
+            c0 = __builtin_amdgcn_fmed3f(m.r * lum, 0.f, 1.f); c1 = __builtin_amdgcn_fmed3f(m.g * lum, 0.f, 1.f); c2 = __builtin_amdgcn_fmed3f(m.b * lum, 0.f, 1.f);
+        } else {
+            gid = -1; depth = 0.f;
+        }
+    }
+    uint8_t* o = out + idx * 3;
+    if (hit) {
+        o[0] = (uint8_t)rintf(255.f * c0); o[1] = (uint8_t)rintf(255.f * c1); o[2] = (uint8_t)rintf(255.f * c2);
+    } else if (frame) {
+        const uint8_t* fr = frame + r * 3;
+        o[0] = fr[0]; o[1] = fr[1]; o[2] = fr[2];
+    } else {
+        o[0] = 0; o[1] = 0; o[2] = 0;
+    }
+    if (color_out) { color_out[idx * 3] = c0; color_out[idx * 3 + 1] = c1; color_out[idx * 3 + 2] = c2; }
+    if (face_out) face_out[idx] = gid;
+    if (depth_out) depth_out[idx] = depth;
+}
+
+// verts [P, V, 3] fp32 (mesh frame, as WHMR.forward returns them); faces [F, 3] int32 with every index in [0, V) (the caller checks); vf_ptr [V + 1],
+// vf_idx [3 F] int32: vertex -> face CSR; cam_t [P, 3]; focal [P, 2] = (fx, fy); rot [9] HOST floats (camera_rotation, row-major) or null = identity;
+// side_cos / side_sin of sideview_angle; frame [H, W, 3] uint8 or null (black); per_person: one image per person instead of one shared depth buffer;
+// base colour, ambient, k_d, (lx, ly, lz) = unit direction TO the light in the world frame.  Scratch: scr, nrm [P, V, 3] fp32 (scr = (u, v, depth) of
+// every vertex on return), zbuf [NI, H, W] uint64, NI = per_person ? P : 1.  out [NI, H, W, 3] uint8; optional (or null) color_out [NI, H, W, 3] fp32
+// (0 on the background), face_out [NI, H, W] int32 (global face id person * F + face, -1 = background), depth_out [NI, H, W] fp32 (0 = background).
+extern "C" int whmr_mesh_render(const float* verts, int P, int V, const int32_t* faces, int F, const int32_t* vf_ptr, const int32_t* vf_idx,
+                                const float* cam_t, const float* focal, float cx, float cy, const float* rot, float side_cos, float side_sin, float znear,
+                                const uint8_t* frame, int H, int W, int per_person, float base_r, float base_g, float base_b, float ambient, float k_d,
+                                float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, uint8_t* out, float* color_out, int32_t* face_out,
+                                float* depth_out, void* stream) {
+    if (P <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0 || (long)P * F > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int NI = per_person ? P : 1;
+    const long npix = (long)NI * H * W;
+    mesh_cam c{cx, cy, side_cos, side_sin, rot != nullptr, {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}};
+    if (rot)
+        for (int k = 0; k < 9; ++k) c.r[k] = rot[k];
+    mesh_shade m{base_r, base_g, base_b, ambient, k_d, lx, ly, lz};
+    const long n0 = (long)P * V > npix ? (long)P * V : npix;
+    hipLaunchKernelGGL(mesh_vertex_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, verts, faces, vf_ptr, vf_idx, cam_t, focal, scr, nrm,
+                       (unsigned long long*)zbuf, npix, P, V, c);
+    WHMR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mesh_faces_kernel, dim3((unsigned)(((long)P * F + 255) / 256)), dim3(256), 0, st, scr, faces, (unsigned long long*)zbuf, P, V, F, H, W,
+                       per_person, znear);
+    WHMR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mesh_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, scr, nrm, faces, (const unsigned long long*)zbuf, frame,
+                       out, color_out, face_out, depth_out, NI, V, F, H, W, m);
+    WHMR_CHECK_LAUNCH();
+    return 0;
+}

@@ -64,16 +64,31 @@ def infer_frame(model, frame_u8, dets, with_full_image=True):
                  orig_shape=kw['orig_shape'], bbox_info=kw['bbox_info'], is_train=False, J_regressor=None, full_x=kw['full_x'])
 
 
+@torch.no_grad()
+def render_frame(out, frame_u8, renderer, per_person=False):
+    """The picture of a frame (tester.py:176-214, overlay panel): ``local_smpl_vertices`` of the vis_dict ``out`` drawn over ``frame_u8`` with
+    ``pred_cam_t`` / ``focal_length``, identity camera rotation (tester.py:194) and the frame centre (:185) by ``renderer``
+    (utils.renderer_cam.MeshRenderer).  uint8 [H, W, 3] with all persons in one depth buffer, or [P, H, W, 3] with per_person.  No host sync."""
+    if isinstance(frame_u8, np.ndarray):
+        frame_u8 = torch.from_numpy(np.ascontiguousarray(frame_u8)).cuda()
+    return renderer.render(frame_u8, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], per_person=per_person)
+
+
 class FramePipeline:
     """infer_frame with the model call (cam_model + W-HMR forward, ~200 launches) replayed from a HIP graph per (number of persons,
-    full-image size): at one to a few persons per frame the eager path is bound by Python launch overhead, not by the GPU."""
+    full-image size): at one to a few persons per frame the eager path is bound by Python launch overhead, not by the GPU.
+    With ``renderer`` (utils.renderer_cam.MeshRenderer) the call returns (vis_dict, image): the overlay is launched right behind the replayed graph on
+    the same stream, with no host sync between model and picture."""
 
-    def __init__(self, model, with_full_image=True):
+    def __init__(self, model, with_full_image=True, renderer=None, per_person=False):
         self.model, self.with_full_image, self._graphs = model, with_full_image, {}
+        self.renderer, self.per_person = renderer, per_person
 
     @torch.no_grad()
     def __call__(self, frame_u8, dets):
         from .graph import GraphedForward
+        if self.renderer is not None and isinstance(frame_u8, np.ndarray):
+            frame_u8 = torch.from_numpy(np.ascontiguousarray(frame_u8)).cuda()             # uploaded once for crops and picture
         kw = prepare_frame(frame_u8, dets, self.with_full_image)
         key = (kw['x'].shape[0], tuple(kw['full_x'].shape) if kw['full_x'] is not None else None)
         call = dict(x=kw['x'], meta_masks=None, center=kw['center'], scale=kw['scale'], bbox_height=kw['bbox_height'],
@@ -81,4 +96,7 @@ class FramePipeline:
         g = self._graphs.get(key)
         if g is None:
             g = self._graphs[key] = GraphedForward(self.model, **call)
-        return g(**call)
+        out = g(**call)
+        if self.renderer is None:
+            return out
+        return out, render_frame(out, frame_u8, self.renderer, self.per_person)
