@@ -594,6 +594,32 @@ int whmr_mesh_render(const float* verts, int P, int V, const int32_t* faces, int
                      float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, uint8_t* out, float* color_out, int32_t* face_out,
                      float* depth_out, void* stream);
 
+/* ---- training input side (csrc/augment.hip): the sample-making of BaseDataset.__getitem__ (datasets/base_dataset.py:249-384) for a whole batch --
+ * rgb_processing (:183-207) over utils/imutils.py:crop (:54-88: integer box, skimage rotate, Pillow bicubic resize), Normalize and the
+ * [:, :, 32:-32] slice; j2d / j3d / pose_processing (:209-247), keypoints_world, bbox_info and the scalars (:294-373).
+ * items: DEVICE array of B whmr_augment_item, the per-sample geometry the host computes in float64 as the reference does (whmr_amd.datasets.
+ * train_batch.TrainBatchMaker packs it): box of rot = 0 [ul, ul + (bw, bh)), pad (0 <=> rot = 0), T = get_transform with rot, M = the
+ * rotation's inverse map in padded-box pixels, ksize_x / ksize_y = 2 ceil(2 max(1, bw|bh / 256)) + 1, and this sample's slices of the scratch buffers:
+ * rot_off into rot_scratch (bw * bh * 3 bytes, samples with rot != 0), mid_off into mid_scratch (bh * 192 * 3 bytes), coef_off into coef_scratch
+ * (256 * (4 + ksize_x + ksize_y) int32).  Reads outside a source image return zero.  out [B, 3, 256, 192] fp32; raw (nullable) [B, 256, 192, 3]
+ * uint8 = the patch before / 255.  Four launches (three when any_rot is 0), no allocation, no synchronisation, bit-reproducible. */
+struct whmr_augment_item {
+    const uint8_t* img; int64_t row_stride, sample_index, rot_off, mid_off, coef_off;
+    int32_t H, W, ul_x, ul_y, bw, bh, pad, flip, is_smpl, ksize_x, ksize_y, reserved;
+    double T[9], M[6], j3d_cs[2], aa_cs[2], pn[3], rot, scale, center[2];
+};
+int whmr_augment_crop(const void* items, int B, int max_box_w, int max_box_h, int any_rot, void* rot_scratch, void* mid_scratch,
+                      int32_t* coef_scratch, float* out, uint8_t* raw, const float* mean3, const float* std3, void* stream);
+/* Labels of the same batch: one workgroup per sample, float64.  io (HOST struct of DEVICE pointers): the resident annotation arrays (float64;
+ * S and smpl_2dkps nullable = absent from the dataset), mask [B, 431] bytes, and one output per key of the batch dictionary. */
+struct whmr_augment_labels_io {
+    const double *pose, *betas, *keypoints, *S, *smpl_2dkps; const float* has_smpl; const int32_t* gender; const uint8_t* mask;
+    float *o_pose, *o_betas, *o_keypoints, *o_keypoints_world, *o_smpl_2dkps, *o_pose_3d, *o_meta_mask, *o_has_smpl;
+    double* o_scale; float* o_center; int64_t *o_orig_shape, *o_is_flipped; float* o_rot_angle; int32_t* o_gender; int64_t* o_sample_index;
+    float *o_bbox_height, *o_bbox_width, *o_focal, *o_bbox_info; int64_t* o_has_pose_3d;
+};
+int whmr_augment_labels(const void* items, int B, const struct whmr_augment_labels_io* io, void* stream);
+
 /* ---- attainable ceilings of the box the benchmark runs on (csrc/ceilings.hip; SURVEY 8(d) "datasheet numbers AND measure on the box"); replaces no
  * reference code -- bench.py calls them after its timed region and reports them as roofline.attainable / sclk_mhz_observed.
  * whmr_mfma_ceiling: `blocks` workgroups x 4 waves, each `iters` x 8 register-fed v_mfma_f32_16x16x32_bf16 on random operands

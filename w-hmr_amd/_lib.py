@@ -68,6 +68,18 @@ class WhmrMafWeights(C.Structure):
                 ('w2t', C.c_void_p), ('b2', C.c_void_p), ('w0b', C.c_void_p), ('w1b', C.c_void_p), ('w2b', C.c_void_p)]
 
 
+class _WhmrAugmentLabelsIO(C.Structure):
+    """struct whmr_augment_labels_io (include/whmr_hip.h): resident annotation arrays and the outputs of whmr_augment_labels"""
+    _fields_ = [(k, C.c_void_p) for k in (
+        'pose', 'betas', 'keypoints', 'S', 'smpl_2dkps', 'has_smpl', 'gender', 'mask',
+        'o_pose', 'o_betas', 'o_keypoints', 'o_keypoints_world', 'o_smpl_2dkps', 'o_pose_3d', 'o_meta_mask', 'o_has_smpl', 'o_scale', 'o_center',
+        'o_orig_shape', 'o_is_flipped', 'o_rot_angle', 'o_gender', 'o_sample_index', 'o_bbox_height', 'o_bbox_width', 'o_focal', 'o_bbox_info',
+        'o_has_pose_3d')]
+
+
+AUGMENT_ITEM_FORMAT = '<Q5q12i26d'          # struct whmr_augment_item (include/whmr_hip.h), 304 bytes
+
+
 class WhmrTnItem(C.Structure):
     """struct whmr_tn_item (include/whmr_hip.h): one product of a grouped weight-gradient launch"""
     _fields_ = [('A', C.c_void_p), ('lda', C.c_long), ('B', C.c_void_p), ('ldb', C.c_long), ('C', C.c_void_p), ('ldc', C.c_long),
@@ -180,6 +192,8 @@ _SIGS = {
     'whmr_iuv_losses': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     'whmr_iuv_losses_bwd': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _L, _P],
     'whmr_weights_prepare': [_P, _I, _I, _P],
+    'whmr_augment_crop': [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    'whmr_augment_labels': [_P, _I, C.POINTER(_WhmrAugmentLabelsIO), _P],
     'whmr_maxpool_nhwc': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'whmr_avgpool_nhwc': [_P, _P, _I, _I, _I, _I, _P],
 }
@@ -1249,6 +1263,22 @@ def crop_normalize(frame, inv_affine, patch_w, patch_h, x0, x1, out, raw, mean, 
     _check(lib().whmr_crop_normalize(frame.data_ptr(), H, W, frame.stride(0), inv_affine.data_ptr(), inv_affine.shape[0], patch_w, patch_h,
                                      x0, x1, out.data_ptr(), _ptr(raw), m3, s3, _stream()), 'whmr_crop_normalize')
     return out
+
+
+def augment_crop(items, B, max_box_w, max_box_h, any_rot, rot_scratch, mid_scratch, coef_scratch, out, raw, mean, std):
+    """image half of the training-batch maker (include/whmr_hip.h: whmr_augment_crop); items: the uploaded table of B whmr_augment_item"""
+    _dev(items, rot_scratch, mid_scratch, coef_scratch, out, raw)
+    assert out.dtype == torch.float32 and out.is_contiguous() and coef_scratch.dtype == torch.int32
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    _check(lib().whmr_augment_crop(items.data_ptr(), B, max_box_w, max_box_h, int(any_rot), _ptr(rot_scratch), mid_scratch.data_ptr(),
+                                   coef_scratch.data_ptr(), out.data_ptr(), _ptr(raw), m3, s3, _stream()), 'whmr_augment_crop')
+    return out
+
+
+def augment_labels(items, B, io):
+    """label half (whmr_augment_labels); io: a filled _WhmrAugmentLabelsIO"""
+    _dev(items)
+    _check(lib().whmr_augment_labels(items.data_ptr(), B, C.byref(io), _stream()), 'whmr_augment_labels')
 
 
 def attention_x3_set_variant(old_kernel):

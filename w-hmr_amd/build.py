@@ -22,7 +22,7 @@ def _stale(target, deps):
 # streams (the host pass prints "not a recognized feature" for the flag and ignores it).
 _NO_PK = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 NO_PACKED_FP32 = {f: _NO_PK for f in ('smpl_lbs.hip', 'smpl_fused.hip', 'geometry.hip', 'iuv_loss.hip', 'maf_sampler.hip', 'rasterize.hip', 'vit_ops.hip',
-                                         'pose_eval.hip', 'mesh_render.hip')}
+                                         'pose_eval.hip', 'mesh_render.hip', 'augment.hip')}
 if os.environ.get('WHMR_BUILD_PACKED_FP32', '0') == '1':                 # A/B
     NO_PACKED_FP32 = {}
 

@@ -15,3 +15,15 @@ EXTRA_VERTEX_IDS = [332, 6260, 2800, 4071, 583, 3216, 3226, 3387, 6617, 6624, 67
 SMPL_PARENTS = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21]
 H36M_TO_J17 = [6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10, 0, 7, 9]
 H36M_TO_J14 = H36M_TO_J17[:14]
+
+# Left / right mirror of the joint sets (augmentation flip; values of core/constants.py:106-118 in the reference, stated per convention):
+# out[i] = in[PERM[i]].  SMPL's 24 kinematic joints: pelvis, spine and head chain stay, every left / right pair (hips 1 / 2, knees 4 / 5, ankles
+# 7 / 8, feet 10 / 11, collars 13 / 14, shoulders 16 / 17, elbows 18 / 19, wrists 20 / 21, hands 22 / 23) swaps.
+SMPL_JOINTS_FLIP_PERM = [0, 2, 1, 3, 5, 4, 6, 8, 7, 9, 11, 10, 12, 14, 13, 15, 17, 16, 19, 18, 21, 20, 23, 22]
+SMPL_POSE_FLIP_PERM = [3 * j + k for j in SMPL_JOINTS_FLIP_PERM for k in range(3)]           # the 72 axis-angle components, joint by joint
+# the 24 dataset joints (right leg 0-2 <-> left leg 5-3, right arm 6-8 <-> left arm 11-9, neck .. head top stay, eyes 19 / 20 and ears 21 / 22 ... swap)
+J24_FLIP_PERM = [5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13, 14, 15, 16, 17, 18, 19, 21, 20, 23, 22]
+# the 25 OpenPose joints (arms 2-4 <-> 5-7, legs 9-11 <-> 12-14, eyes, ears, feet 19-21 <-> 22-24)
+OPENPOSE25_FLIP_PERM = [0, 1, 5, 6, 7, 2, 3, 4, 8, 12, 13, 14, 9, 10, 11, 16, 15, 18, 17, 22, 23, 24, 19, 20, 21]
+J49_FLIP_PERM = OPENPOSE25_FLIP_PERM + [25 + j for j in J24_FLIP_PERM]
+SMPL_J49_FLIP_PERM = OPENPOSE25_FLIP_PERM + [25 + j for j in SMPL_JOINTS_FLIP_PERM]
