@@ -202,7 +202,7 @@ static int launch_x3(const void* qh, const void* ql, void* oh, void* ol, int B, 
 }
 
 int whmr_attention_blk16_x3_launch(const void* qh, const void* ql, void* oh, void* ol, int B, int N, int H, float scale, hipStream_t st, int lab);      // attention_blk16.hip
-static int g_x3_old = 0;       // whmr_set_option(120, 1): the round-3 kernel above instead of the persistent 16-row-tile one (A/B, tests)
+static int g_x3_old = 0;       // whmr_attention_x3_set_variant(1): the round-3 kernel above instead of the persistent 16-row-tile one (A/B, tests)
 extern "C" int whmr_attention_x3_set_variant(int variant) { g_x3_old = variant; return 0; }
 
 extern "C" int whmr_attention_blk_x3(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int B, int N, int H, float scale, void* stream) {

@@ -21,9 +21,8 @@
 // 8 waves issue their DMA at the same time and the matrix pipes idle for the ~1000 clk the L1 needs to take 64 KiB (qkv main loop
 // 48 -> 36-38 us in the lab).
 #include "gemm_blk16_impl.h"
-// (the 32x32x16 kernel of gemm_blk_impl.h now only exists for split-bf16 operands: gemm_blk_x3.hip.  Its bf16 instantiation -- the A/B partner of
-// round 3, WHMR_BLK_MFMA=32 -- the two-barrier schedule and the W-direct main loop are no longer compiled: DESIGN 6 keeps their numbers.)
-__attribute__((visibility("hidden"))) int blk_x3_launch_tile(const whmr_gemm_blk_desc* pp, int tile, void* stream, int sched);
+// (the 32x32x16 kernel of gemm_blk_impl.h is the split-bf16 kernel and nothing else: gemm_blk_x3.hip.  Its bf16 instantiation -- the A/B partner of
+// round 3, WHMR_BLK_MFMA=32 -- the two-barrier schedule and the W-direct main loop no longer exist: DESIGN 6 keeps their numbers.)
 
 #ifdef WHMR_BLK_STAMPS
 // lab build only (tools/gemm_stamps.py): every bf16 blocked launch takes the next [tiles][2][8] u64 record of a caller-provided device buffer
@@ -57,12 +56,12 @@ extern "C" int whmr_gemm_blk_tile(const whmr_gemm_blk_desc* pp, int tile, void* 
     if (p.A_lo || p.W_lo || p.C_lo) {
         // split-bf16 operands: both lo halves, a lo output for the bf16 epilogues, a lo half of the folded-LayerNorm operand copy
         if (!p.A_lo || !p.W_lo || (p.epi < 2 && !p.C_lo) || (p.xhat && !p.xhat_lo)) return (int)hipErrorInvalidValue;
-        return blk_x3_launch_tile(pp, tile, stream, 1);
+        return blk_x3_launch_tile(pp, tile, stream);
     }
     return blk16_launch_tile(p, tile, (hipStream_t)stream);
 }
 
-static int g_blk_force[4] = {0, 0, 0, 0};                   // whmr_set_option keys 110..113: tile for N = 2304 / (768, K <= 1024) / 3072 / (768, K > 1024)
+static int g_blk_force[4] = {0, 0, 0, 0};                   // whmr_gemm_blk_set_tile slots 0..3: tile for N = 2304 / (768, K <= 1024) / 3072 / (768, K > 1024)
 extern "C" int whmr_gemm_blk_set_tile(int slot, int tile) {
     if (slot < 0 || slot > 3) return (int)hipErrorInvalidValue;
     g_blk_force[slot] = tile;

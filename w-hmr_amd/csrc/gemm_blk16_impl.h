@@ -17,8 +17,6 @@
 // DMA's SOURCE side (a lane of the LDS-DMA picks its own 16 bytes inside the same contiguous 512-B unit), so the global access pattern and
 // the conflict-free 256-B-per-16-lanes fragment reads are those of the plain layout.
 #pragma once
-#include <type_traits>
-#include "common.h"
 #include "gemm_blk.h"
 
 // ---- lab instrumentation (tools/gemm_stamps.py; NEVER defined in the product build): per tile and wave group, s_memrealtime (100 MHz, one clock for
@@ -46,43 +44,20 @@ unsigned long long* blk_stamp_next(int tiles);
 #define BLK16_STAMP_ARG(tiles)
 #endif
 
-typedef __attribute__((address_space(3))) void lds16_void_t;
-typedef const __attribute__((address_space(1))) void gbl16_void_t;
-
-template <int N> __device__ __forceinline__ void b16_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void b16_wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-// fragment read hidden from hipcc's waitcnt bookkeeping (valid after the counted wait + sched_barrier that follows it)
-template <int OFF> __device__ __forceinline__ bf16x8_t b16_lds_read128(uint32_t addr) {
-    bf16x8_t v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-
-template <int MI0, int MI1>
-struct blk16_cfg {
-    static constexpr int MB = MI0 + MI1;                 // A row blocks (32 rows) per tile
-    static constexpr int BM = MB * 32, BN = 256;
-    static constexpr int SLOT = (MB + 8) * 2048;         // one half K tile (32 deep) of A and W: 2 KiB per row block
-    static constexpr int HU = (MB + 8) * 2;              // 1-KiB DMA units per half tile
-    static constexpr int HUPW = (HU + 7) / 8;            // units per wave (waves >= HU % 8 issue one less when HU % 8 != 0)
-    static constexpr int BIAS_OFF = 4 * SLOT;            // [256] floats behind the ring, then [256] floats of the LayerNorm-fold column sums
-    static constexpr int STAT_OFF = BIAS_OFF + 2048;     // LayerNorm folding: [BM][4][2] floats -- row statistics (consumer) / per-wave-column partial sums (producer)
-    static constexpr int LDS = 4 * SLOT + 2048 + BM * 32;
-    static constexpr int MIMAX = MI0 > MI1 ? MI0 : MI1;
-};
-
 // One barrier per half tile, the two wave groups in opposite order within a slot.  (Round 3-4 also carried a two-barrier schedule and the same tile on
-// FOUR waves, one per SIMD -- tile id 0x144, bit-identical, same K slope, worse epilogue: profiles/r04_fw4_ab.txt.  Both are gone from the build.)
+// FOUR waves, one per SIMD -- tile id 0x144, bit-identical, same K slope, worse epilogue: profiles/r04_fw4_ab.txt.  Both are gone.)
 // One tile per workgroup, in XCD-aware order.
-template <int MI0, int MI1, int EPI, int SCHED, int NW>
+//
+// The body stays a function of its own although the kernel below is its only caller: written straight into the __global__ function the same
+// statements come out of hipcc with another register allocation and block layout in all 32 instantiations
+// (profiles/blk_gemm_strip_isa_diff.txt), and a change of the emitted code wants a measurement of its own.
+template <int MI0, int MI1, int EPI>
 __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, char* smem BLK16_STAMP_PARAM) {
-    using cfg = blk16_cfg<MI0, MI1>;
-    constexpr int MB = cfg::MB, BM = cfg::BM, BN = cfg::BN, SLOT = cfg::SLOT, HU = cfg::HU, NJ = NW == 8 ? 2 : 4, NT = NW * 64;
-    constexpr int HUPW = (HU + NW - 1) / NW;             // DMA units per wave (waves >= HU % NW issue one less when HU % NW != 0)
-    static_assert(NW == 8 && SCHED == 1, "eight waves, one barrier per half tile");
+    using cfg = blk_cfg<MI0, MI1>;
+    constexpr int MB = cfg::MB, BM = cfg::BM, BN = cfg::BN, SLOT = cfg::SLOT, HU = cfg::HU, HUPW = cfg::HUPW, NJ = 2, NT = 512;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = NW == 8 ? wave >> 2 : wave >> 1, wn = NW == 8 ? wave & 3 : wave & 1;     // NW 8: wm = group
+    const int wm = wave >> 2, wn = wave & 3;              // wm = group
     const int l15 = lane & 15, g = lane >> 4;             // row inside a 16-row half / K chunk of the operand fragments = column group of the results
     const int tiles_n = p.N / BN, tiles_m = (p.M + BM - 1) / BM;
     const int lid = xcd_remap(blockIdx.x, tiles_m * tiles_n);
@@ -94,7 +69,7 @@ __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, cha
     const int KC = p.K >> 3;                              // 16-B chunks per row
     const int H = p.K >> 5;                               // half K tiles (32 deep) = ring slots to walk
     const int rb_last = ((p.M + 31) >> 5) - 1;            // last valid row block
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(lds16_void_t*)smem;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void_t*)smem;
 
     // this tile's bias slice -> LDS (one float per thread, in flight under the whole main loop)
     for (int t = tid; t < 2 * BN; t += NT) {
@@ -115,13 +90,13 @@ __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, cha
 
     // ---- DMA units of this wave: u = wave + 8 i -> row block u >> 1 (A blocks first, then the 8 W blocks), 1-KiB half u & 1 (two 8-deep chunks).
     // A units are copied as they are; inside a W chunk LDS slot s (= lane & 31) receives column 8 ((s & 15) >> 2) + 4 (s >> 4) + (s & 3).
-    const bool dma_full = (HU % NW == 0) || (wave < HU % NW);        // this wave issues HUPW units (else HUPW - 1)
+    const bool dma_full = (HU % 8 == 0) || (wave < HU % 8);        // this wave issues HUPW units (else HUPW - 1)
     const int wslot = lane & 31;
     const int wsrc = (lane & 32) * 16 + (8 * ((wslot & 15) >> 2) + 4 * (wslot >> 4) + (wslot & 3)) * 16;
     const char* hsrc[HUPW];
 #pragma unroll
     for (int i = 0; i < HUPW; ++i) {
-        int u = wave + NW * i;
+        int u = wave + 8 * i;
         if (u >= HU) u = HU - 1;                          // never issued (dma_full is false); keeps the address valid
         const int b = u >> 1, half = u & 1;
         if (b < MB) {
@@ -133,7 +108,7 @@ __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, cha
         }
     }
     auto hpiece = [&](int h, int i) {                     // piece i of half tile h
-        __builtin_amdgcn_global_load_lds((gbl16_void_t*)(hsrc[i] + (size_t)h * 2048), (lds16_void_t*)(smem + (h & 3) * SLOT + (wave + NW * i) * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gbl_void_t*)(hsrc[i] + (size_t)h * 2048), (lds_void_t*)(smem + (h & 3) * SLOT + (wave + 8 * i) * 1024), 16, 0, 0);
     };
     auto hstage = [&](int h) {
 #pragma unroll
@@ -143,9 +118,9 @@ __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, cha
     };
     // own DMA groups still allowed in flight: `young` groups of (HUPW or HUPW - 1) loads
     auto wait_dma = [&](int young) {
-        if (young >= 2) { if (dma_full) b16_wait_vmcnt<2 * HUPW>(); else b16_wait_vmcnt<2 * (HUPW - 1)>(); }
-        else if (young == 1) { if (dma_full) b16_wait_vmcnt<HUPW>(); else b16_wait_vmcnt<HUPW - 1>(); }
-        else b16_wait_vmcnt<0>();
+        if (young >= 2) { if (dma_full) blk_wait_vmcnt<2 * HUPW>(); else blk_wait_vmcnt<2 * (HUPW - 1)>(); }
+        else if (young == 1) { if (dma_full) blk_wait_vmcnt<HUPW>(); else blk_wait_vmcnt<HUPW - 1>(); }
+        else blk_wait_vmcnt<0>();
     };
 
     // acc[i][j][mh][nh]: rows 16 mh + l15 of row block i, columns 8 g + 4 nh + (0..3) of column block j
@@ -172,25 +147,25 @@ __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, cha
     auto main_loop = [&](auto miw_tag) {
         constexpr int MIW = decltype(miw_tag)::value;
         const uint32_t a_b = lds0 + (wm * MI0) * 2048 + g * 512 + l15 * 16;
-        const uint32_t b_b = lds0 + (MB + wn * NJ) * 2048 + g * 512 + l15 * 16;
+        const uint32_t b_b = lds0 + (MB + wn * 2) * 2048 + g * 512 + l15 * 16;
         bf16x8_t fa[MIW][2], fb[NJ][2];                    // [.][mh] rows 16 mh.. of the A block;  [.][nh] LDS slots 16 nh.. of the W block
         auto MEM = [&](int x) {
             const uint32_t sa = a_b + (x & 3) * SLOT, sb = b_b + (x & 3) * SLOT;
-            fb[0][0] = b16_lds_read128<0>(sb); fb[1][0] = b16_lds_read128<2048>(sb);
-            fa[0][0] = b16_lds_read128<0>(sa);
-            if constexpr (MIW > 1) fa[1][0] = b16_lds_read128<2048>(sa);
-            if constexpr (MIW > 2) fa[2][0] = b16_lds_read128<4096>(sa);
-            if constexpr (MIW > 3) fa[3][0] = b16_lds_read128<6144>(sa);
-            if constexpr (MIW > 4) fa[4][0] = b16_lds_read128<8192>(sa);
-            fb[0][1] = b16_lds_read128<256>(sb); fb[1][1] = b16_lds_read128<2048 + 256>(sb);
-            fa[0][1] = b16_lds_read128<256>(sa);
-            if constexpr (MIW > 1) fa[1][1] = b16_lds_read128<2048 + 256>(sa);
-            if constexpr (MIW > 2) fa[2][1] = b16_lds_read128<4096 + 256>(sa);
-            if constexpr (MIW > 3) fa[3][1] = b16_lds_read128<6144 + 256>(sa);
-            if constexpr (MIW > 4) fa[4][1] = b16_lds_read128<8192 + 256>(sa);
+            fb[0][0] = blk_lds_read128<0>(sb); fb[1][0] = blk_lds_read128<2048>(sb);
+            fa[0][0] = blk_lds_read128<0>(sa);
+            if constexpr (MIW > 1) fa[1][0] = blk_lds_read128<2048>(sa);
+            if constexpr (MIW > 2) fa[2][0] = blk_lds_read128<4096>(sa);
+            if constexpr (MIW > 3) fa[3][0] = blk_lds_read128<6144>(sa);
+            if constexpr (MIW > 4) fa[4][0] = blk_lds_read128<8192>(sa);
+            fb[0][1] = blk_lds_read128<256>(sb); fb[1][1] = blk_lds_read128<2048 + 256>(sb);
+            fa[0][1] = blk_lds_read128<256>(sa);
+            if constexpr (MIW > 1) fa[1][1] = blk_lds_read128<2048 + 256>(sa);
+            if constexpr (MIW > 2) fa[2][1] = blk_lds_read128<4096 + 256>(sa);
+            if constexpr (MIW > 3) fa[3][1] = blk_lds_read128<6144 + 256>(sa);
+            if constexpr (MIW > 4) fa[4][1] = blk_lds_read128<8192 + 256>(sa);
             if (x + 3 < H) hstage(x + 3);
             wait_dma(H - 2 - x);                                       // own share of half tile x + 1 has landed (x + 2, x + 3 may fly)
-            b16_wait_lgkmcnt<0>();
+            blk_wait_lgkmcnt<0>();
             __builtin_amdgcn_sched_barrier(0);
         };
         auto MFMA = [&]() {
@@ -206,29 +181,15 @@ __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, cha
                             acc[i][j][a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][b], fa[i][a], acc[i][j][a][b], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         };
-        if constexpr (SCHED == 1) {
-            MEM(0);
-            if (wm == 1) MFMA();                                           // group 1 is half a slot ahead
-            for (int k = 0; k < H; ++k) {
-                __builtin_amdgcn_s_barrier();
-                if (wm == 0) MFMA();                                       // MFMA(k)
-                if (k + 1 < H) {
-                    MEM(k + 1);
-                    if (wm == 1) MFMA();                                   // MFMA(k + 1)
-                }
+        MEM(0);
+        if (wm == 1) MFMA();                                               // group 1 is half a slot ahead
+        for (int k = 0; k < H; ++k) {
+            __builtin_amdgcn_s_barrier();
+            if (wm == 0) MFMA();                                           // MFMA(k)
+            if (k + 1 < H) {
+                MEM(k + 1);
+                if (wm == 1) MFMA();                                       // MFMA(k + 1)
             }
-        } else {
-            // two barriers per half tile: MEM(h) of one group beside MFMA(h) of the other, rendezvous after each; group 1 one barrier behind
-            if (wm == 1) __builtin_amdgcn_s_barrier();
-            for (int h = 0; h < H; ++h) {
-                MEM(h);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_s_setprio(1);
-                MFMA();
-                __builtin_amdgcn_s_setprio(0);
-                __builtin_amdgcn_s_barrier();
-            }
-            if (wm == 0) __builtin_amdgcn_s_barrier();
         }
     };
     if constexpr (MI0 == MI1) {
@@ -244,8 +205,8 @@ __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, cha
     const int miw = wm == 0 ? MI0 : MI1;
     const int rb0 = (m0 >> 5) + (wm == 0 ? 0 : MI0);                   // first row block of this wave
     const int rw0 = wm == 0 ? 0 : MI0 * 32;                           // its first row inside the tile
-    const int nb0 = n0 + wn * (NJ * 32);
-    const float* sBias = (const float*)(smem + cfg::BIAS_OFF) + wn * (NJ * 32);
+    const int nb0 = n0 + wn * 64;
+    const float* sBias = (const float*)(smem + cfg::BIAS_OFF) + wn * 64;
     if constexpr (EPI == 0 || EPI == 1) {
         const int NC8 = p.N >> 3;
         const bool fold = p.stats_in != nullptr;                        // LayerNorm folded into this GEMM: per-row (rstd, rstd * mean)
@@ -301,8 +262,8 @@ __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, cha
     } else {
         const int NC4 = p.N >> 2;
         const bool emit = p.xhat != nullptr;                            // also write bf16(C) as the next GEMM's operand + row partial sums
-        // row partial sums per PAIR of column blocks (64 columns: one wave column of the eight-wave kernel) -- the four-wave body keeps two of
-        // them per row so that the sums are taken in the same order whatever kernel ran the tile
+        // row partial sums per PAIR of column blocks (64 columns = this wave's column; the index is kept because dropping it moves hipcc's
+        // register allocation in the MI0 != MI1 producers)
         float sx[cfg::MIMAX][2][NJ / 2], sxx[cfg::MIMAX][2][NJ / 2], sh[cfg::MIMAX][2];
 #pragma unroll
         for (int i = 0; i < cfg::MIMAX; ++i)
@@ -417,16 +378,16 @@ __device__ __forceinline__ void gemm_blk16_body(const whmr_gemm_blk_desc& p, cha
 #endif
 }
 
-template <int MI0, int MI1, int EPI, int SCHED>
+template <int MI0, int MI1, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_blk16_kernel(const whmr_gemm_blk_desc p BLK16_STAMP_PARAM) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    gemm_blk16_body<MI0, MI1, EPI, SCHED, 8>(p, smem BLK16_STAMP_PASS);
+    gemm_blk16_body<MI0, MI1, EPI>(p, smem BLK16_STAMP_PASS);
 }
 
-template <int MI0, int MI1, int EPI, int SCHED>
-static int launch_blk16_s(const whmr_gemm_blk_desc& p, hipStream_t st) {
-    using cfg = blk16_cfg<MI0, MI1>;
-    auto kern = gemm_blk16_kernel<MI0, MI1, EPI, SCHED>;
+template <int MI0, int MI1, int EPI>
+static int launch_blk16(const whmr_gemm_blk_desc& p, hipStream_t st) {
+    using cfg = blk_cfg<MI0, MI1>;
+    auto kern = gemm_blk16_kernel<MI0, MI1, EPI>;
     static bool attr_done = false;
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, cfg::LDS);
@@ -439,28 +400,8 @@ static int launch_blk16_s(const whmr_gemm_blk_desc& p, hipStream_t st) {
     return 0;
 }
 
-template <int MI0, int MI1>
-static int launch_blk16_epi(const whmr_gemm_blk_desc& p, hipStream_t st) {
-    switch (p.epi) {
-        case 0: return launch_blk16_s<MI0, MI1, 0, 1>(p, st);
-        case 1: return launch_blk16_s<MI0, MI1, 1, 1>(p, st);
-        case 2: return launch_blk16_s<MI0, MI1, 2, 1>(p, st);
-        case 3: return launch_blk16_s<MI0, MI1, 3, 1>(p, st);
-    }
-    return (int)hipErrorInvalidValue;
-}
-
-// Tile heights (x 256 columns): the wave rows own MI0 and MI1 row blocks.
 static int blk16_launch_tile(const whmr_gemm_blk_desc& p, int tile, hipStream_t st) {
-    switch (tile) {
-        case 0x44: return launch_blk16_epi<4, 4>(p, st);      // 256 x 256
-        case 0x55: return launch_blk16_epi<5, 5>(p, st);      // 320 x 256
-        case 0x43: return launch_blk16_epi<4, 3>(p, st);      // 224 x 256
-        case 0x33: return launch_blk16_epi<3, 3>(p, st);      // 192 x 256
-        case 0x32: return launch_blk16_epi<3, 2>(p, st);      // 160 x 256
-        case 0x22: return launch_blk16_epi<2, 2>(p, st);      // 128 x 256
-        case 0x54: return launch_blk16_epi<5, 4>(p, st);      // 288 x 256
-        case 0x21: return launch_blk16_epi<2, 1>(p, st);      // 96 x 256: ViT-L at 32 crops (6144 tokens) x N = 1024 is exactly 256 such tiles
-    }
-    return (int)hipErrorInvalidValue;
+    return blk_dispatch_tile(tile, [&](auto mi0, auto mi1) {
+        return blk_dispatch_epi(p.epi, [&](auto epi) { return launch_blk16<decltype(mi0)::value, decltype(mi1)::value, decltype(epi)::value>(p, st); });
+    });
 }

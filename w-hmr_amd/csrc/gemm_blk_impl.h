@@ -1,7 +1,7 @@
-// Kernel template + launchers of the blocked-layout MFMA GEMM, shared by gemm_blk.hip (bf16 operands) and gemm_blk_x3.hip (split-bf16
-// operands: X3 = true).  See gemm_blk.hip for the layout and the schedule.
+// Split-bf16 ("bf16x3") kernel + launchers of the blocked-layout MFMA GEMM on v_mfma_f32_32x32x16_bf16 (gemm_blk_x3.hip instantiates it; the
+// bf16 kernel is gemm_blk16_impl.h).  See gemm_blk.hip for the layout and the schedule.
 //
-// X3 ("bf16x3", the parity-grade numerics of the ViT inference path): every operand is a PAIR of blocked bf16 matrices, x = x_hi + x_lo with
+// bf16x3 (the parity-grade numerics of the ViT inference path): every operand is a PAIR of blocked bf16 matrices, x = x_hi + x_lo with
 // x_hi = bf16(x), x_lo = bf16(x - x_hi) (16 significand bits), and a product is three MFMAs per fragment pair,
 //     a.w ~= a_hi.w_hi + a_lo.w_hi + a_hi.w_lo          (the dropped a_lo.w_lo term is 2^-16 of the product),
 // accumulated in fp32 -- fp32-grade results at a third of the bf16 MFMA rate, several times the exact-f32 MFMA path.  The ring slot keeps
@@ -10,46 +10,17 @@
 // MFMA phase differ: 24 MFMAs (MI = 4) against the same 12 ds_reads + DMA share per phase.  In the bf16 kernel a wave's MEM phase (12 fragment
 // reads + its 4 LDS-DMA pieces, each ~100-185 cycles to issue inside a busy phase: MI355X_MICROARCH.md, + the counted waits) outlasts its partner's
 // 512-cycle MFMA phase; here the MFMA phase is 768 cycles and covers it, so the loop is MFMA-bound.
+//
+// W through LDS, one barrier per half tile, is the only form.  A "W direct" main loop (each wave loads its 64 weight columns from global memory / L2
+// straight into registers, the ring holds only A) measured 3-4 % SLOWER: the texture path carries the same bytes either way, and two
+// half tiles of prefetch distance do not cover a global load's latency under load.  It, the two-barrier schedule and the plain-bf16 branches of this
+// body are gone; last version: `git show 9bcd899:w-hmr_amd/csrc/gemm_blk_impl.h`.
 #pragma once
-#include <type_traits>
-#include "common.h"
 #include "gemm_blk.h"
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void gbl_void_t;
-
-template <int N> __device__ __forceinline__ void blk_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void blk_wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-// fragment read hidden from hipcc's waitcnt bookkeeping (valid after the counted wait + sched_barrier that follows it)
-template <int OFF> __device__ __forceinline__ bf16x8_t blk_lds_read128(uint32_t addr) {
-    bf16x8_t v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-
-// WD ("W direct"): the weight fragments never touch LDS -- each wave loads its own 64 columns of W straight from global memory / L2 into
-// registers (a blocked 1-KiB unit IS an MFMA operand: one coalesced global_load_dwordx4 per fragment), three half tiles deep; the ring holds only A
-// and a wave issues 2 LDS-DMA pieces + 4 register loads per phase instead of 4 pieces, and reads 8 fragments from LDS instead of 12.  Measured
-// 3-4 % SLOWER than the LDS-staged loop: the texture path carries the same bytes either way, and two half tiles of prefetch distance do
-// not cover a global load's latency under load (a fourth register set does not fit).  Kept as schedule 2 for A/B runs; bit-identical results.
-template <int MI0, int MI1, bool WD = false>
-struct blk_cfg {
-    static constexpr int MB = MI0 + MI1;                 // A row blocks (32 rows) per tile
-    static constexpr int BM = MB * 32, BN = 256;
-    static constexpr int NBL = WD ? 0 : 8;               // W row blocks staged through LDS
-    static constexpr int SLOT = (MB + NBL) * 2048;       // one half K tile (32 deep) of A (and W): 2 KiB per row block
-    static constexpr int HU = (MB + NBL) * 2;            // 1-KiB DMA units per half tile
-    static constexpr int HUPW = (HU + 7) / 8;            // units per wave (waves >= HU % 8 issue one less when HU % 8 != 0)
-    static constexpr int BIAS_OFF = 4 * SLOT;            // [256] floats behind the ring, then [256] floats of the LayerNorm-fold column sums
-    static constexpr int STAT_OFF = BIAS_OFF + 2048;     // LayerNorm folding: [BM][4][2] floats -- row statistics (consumer) / per-wave-column partial sums (producer)
-    static constexpr int LDS = 4 * SLOT + 2048 + BM * 32;
-    static constexpr int MIMAX = MI0 > MI1 ? MI0 : MI1;
-};
-
-// SCHED 1: one barrier per half tile, groups in opposite order within a slot;  SCHED 0: two barriers per half tile (MEM | MFMA rendezvous)
-template <int MI0, int MI1, int EPI, int SCHED, bool X3 = false, bool WD = false>
+template <int MI0, int MI1, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_desc p) {
-    using cfg = blk_cfg<MI0, MI1, WD>;
+    using cfg = blk_cfg<MI0, MI1>;
     constexpr int MB = cfg::MB, BM = cfg::BM, BN = cfg::BN, SLOT = cfg::SLOT, HU = cfg::HU, HUPW = cfg::HUPW, NJ = 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -61,7 +32,7 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
     const int tm = lid / tiles_n, tn = lid % tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     const int KC = p.K >> 3;                              // 16-B chunks per row
-    const int H = X3 ? (p.K >> 4) : (p.K >> 5);           // ring slots to walk: half K tiles (32 deep); X3: 16-deep slices, hi | lo units side by side
+    const int H = p.K >> 4;                               // ring slots to walk: 16-deep K slices, the hi | lo units of a row block side by side
     const int rb_last = ((p.M + 31) >> 5) - 1;            // last valid row block
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void_t*)smem;
 
@@ -80,7 +51,7 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
         }
     }
 
-    // ---- DMA units of this wave: u = wave + 8 i -> row block u >> 1 (A blocks first, then the 8 W blocks), 1-KiB half u & 1
+    // ---- DMA units of this wave: u = wave + 8 i -> row block u >> 1 (A blocks first, then the 8 W blocks), 1-KiB unit u & 1 (0 = hi, 1 = lo)
     const bool dma_full = (HU % 8 == 0) || (wave < HU % 8);          // this wave issues HUPW units (else HUPW - 1)
     const char* hsrc[HUPW];
 #pragma unroll
@@ -91,9 +62,9 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
         if (b < MB) {
             int rb = (m0 >> 5) + b;
             if (rb > rb_last) rb = rb_last;               // M tail: re-read the last block (its results are not stored)
-            hsrc[i] = (const char*)((X3 && half) ? p.A_lo : p.A) + ((size_t)rb * KC) * 512 + (X3 ? 0 : half * 1024) + lane * 16;
+            hsrc[i] = (const char*)(half ? p.A_lo : p.A) + ((size_t)rb * KC) * 512 + lane * 16;
         } else {
-            hsrc[i] = (const char*)((X3 && half) ? p.W_lo : p.W) + ((size_t)((n0 >> 5) + b - MB) * KC) * 512 + (X3 ? 0 : half * 1024) + lane * 16;
+            hsrc[i] = (const char*)(half ? p.W_lo : p.W) + ((size_t)((n0 >> 5) + b - MB) * KC) * 512 + lane * 16;
         }
     }
     auto hstage = [&](int h) {
@@ -101,7 +72,7 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
 #pragma unroll
         for (int i = 0; i < HUPW; ++i) {
             if (i < HUPW - 1 || dma_full)
-                __builtin_amdgcn_global_load_lds((gbl_void_t*)(hsrc[i] + (size_t)h * (X3 ? 1024 : 2048)), (lds_void_t*)(smem + slot * SLOT + (wave + 8 * i) * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gbl_void_t*)(hsrc[i] + (size_t)h * 1024), (lds_void_t*)(smem + slot * SLOT + (wave + 8 * i) * 1024), 16, 0, 0);
         }
     };
     // own DMA groups still allowed in flight: `young` groups of (HUPW or HUPW - 1) loads
@@ -119,13 +90,11 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    if constexpr (!WD) {
-        hstage(0);
-        if (H > 1) hstage(1);
-        if (H > 2) hstage(2);
-        wait_dma(H > 2 ? 2 : H - 1);
-        __builtin_amdgcn_s_barrier();
-    }
+    hstage(0);
+    if (H > 1) hstage(1);
+    if (H > 2) hstage(2);
+    wait_dma(H > 2 ? 2 : H - 1);
+    __builtin_amdgcn_s_barrier();
 
     // ONE barrier per half K tile; the two groups walk a slot in opposite order:
     //   slot k:   group 0: MFMA(k), MEM(k+1)      group 1: MEM(k+1), MFMA(k+1)
@@ -133,10 +102,6 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
     // costs MEM + MFMA, not 2 x max(MEM, MFMA) + a second barrier: qkv 53.9 -> 47.2 us in the lab).  Hazards: MEM(x) of both groups
     // lies in slot x-1: it reads ring slot x & 3 (DMA issued in slot x-4, own share awaited in slot x-2, then a barrier) and refills ring
     // slot (x-1) & 3, last read in slot x-2 by MEM(x-1) -- whose ds_reads are drained (lgkmcnt(0)) before the barrier that ends that slot.
-    // W direct: the wave's 64 weight columns, as an SGPR base + the lane's 16-B offset
-    const uint32_t lane16 = lane * 16;
-    const uint64_t wbase = (uint64_t)(uintptr_t)p.W + ((uint64_t)((n0 >> 5) + wn * NJ) * KC) * 512;
-    const uint64_t wbase_lo = X3 ? (uint64_t)(uintptr_t)p.W_lo + ((uint64_t)((n0 >> 5) + wn * NJ) * KC) * 512 : wbase;
     auto main_loop = [&](auto miw_tag) {
         constexpr int MIW = decltype(miw_tag)::value;
         const uint32_t a_b = lds0 + (wm * MI0) * 2048 + hi * 512 + l31 * 16;
@@ -163,159 +128,25 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
         };
         auto MFMA = [&]() {
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (X3) {
-                // [.][0] = hi, [.][1] = lo of the same 16-deep slice: w_hi.a_lo, w_lo.a_hi (the small terms first), then w_hi.a_hi
+            // [.][0] = hi, [.][1] = lo of the same 16-deep slice: w_hi.a_lo, w_lo.a_hi (the small terms first), then w_hi.a_hi
 #pragma unroll
-                for (int t = 0; t < 3; ++t)
+            for (int t = 0; t < 3; ++t)
 #pragma unroll
-                    for (int i = 0; i < MIW; ++i)
+                for (int i = 0; i < MIW; ++i)
 #pragma unroll
-                        for (int j = 0; j < NJ; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][t == 1 ? 1 : 0], fa[i][t == 0 ? 1 : 0], acc[i][j], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                    for (int i = 0; i < MIW; ++i)
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][kk], fa[i][kk], acc[i][j], 0, 0, 0);
-            }
+                    for (int j = 0; j < NJ; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][t == 1 ? 1 : 0], fa[i][t == 0 ? 1 : 0], acc[i][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         };
-        if constexpr (WD) {
-            // ---- W direct: fbq[set] = the wave's W fragments of half tile h (set = h % 3), requested two half tiles ahead of their MFMA phase.
-            // vmcnt bookkeeping: a wave's loads in issue order are ... B(x+1) DMA(x+2) | B(x+2) DMA(x+3) at the end of MEM(x); everything older
-            // (DMA(x+1): its share of the next LDS slot, B(x): the operands of MFMA(x)) must have landed.
-            static_assert(SCHED == 1, "W direct runs the one-barrier schedule");
-            constexpr int NB4 = 2 * NJ;                                    // B loads per half tile and wave
-            bf16x8_t fbq[3][NJ][2];
-            // The loads are inline asm (SGPR base + the lane's 16-B offset), invisible to hipcc's waitcnt pass like the fragment ds_reads above: seen
-            // as ordinary loads it drains vmcnt to ZERO in front of every MFMA phase and in front of every reload of a set (the loads of a set
-            // cross the loop's back edge), i.e. it waits for the DMA three half tiles ahead.  The counted waits of MEMW cover them.
-            auto gload = [](bf16x8_t& dst, uint64_t base, uint32_t voff, auto off_tag) {
-                constexpr int OFF = decltype(off_tag)::value;
-                const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base), hi32 = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-                const uint64_t sb = ((uint64_t)hi32 << 32) | lo;
-                asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(sb), "n"(OFF));
-            };
-            auto loadB = [&](auto set_tag, int h) {
-                constexpr int SET = decltype(set_tag)::value;
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    if constexpr (X3) {
-                        gload(fbq[SET][j][0], wbase + (uint64_t)j * KC * 512 + (uint64_t)h * 1024, lane16, std::integral_constant<int, 0>{});
-                        gload(fbq[SET][j][1], wbase_lo + (uint64_t)j * KC * 512 + (uint64_t)h * 1024, lane16, std::integral_constant<int, 0>{});
-                    } else {
-                        const uint64_t b = wbase + (uint64_t)j * KC * 512 + (uint64_t)h * 2048;
-                        gload(fbq[SET][j][0], b, lane16, std::integral_constant<int, 0>{});
-                        gload(fbq[SET][j][1], b, lane16, std::integral_constant<int, 1024>{});
-                    }
-                }
-            };
-            auto wait_young = [&](int nd, int nb) {                         // leave nd DMA groups + nb B groups (the youngest loads) in flight
-                constexpr int D1 = HUPW, D0 = HUPW - 1;
-                if (nb >= 2) {
-                    if (nd >= 2) { if (dma_full) blk_wait_vmcnt<2 * D1 + 2 * NB4>(); else blk_wait_vmcnt<2 * D0 + 2 * NB4>(); }
-                    else if (nd == 1) { if (dma_full) blk_wait_vmcnt<D1 + 2 * NB4>(); else blk_wait_vmcnt<D0 + 2 * NB4>(); }
-                    else blk_wait_vmcnt<2 * NB4>();
-                } else if (nb == 1) {
-                    if (nd >= 1) { if (dma_full) blk_wait_vmcnt<D1 + NB4>(); else blk_wait_vmcnt<D0 + NB4>(); }
-                    else blk_wait_vmcnt<NB4>();
-                } else blk_wait_vmcnt<0>();
-            };
-            auto wait_wd = [&](int x) {                                    // end of MEM(x): allow the loads issued in MEM(x-1) and MEM(x) only
-                const int nd = H - 2 - x, nb = H - 1 - x;                   // younger DMA groups (x+2, x+3) / B groups (x+1, x+2) that exist
-                wait_young(nd < 0 ? 0 : nd > 2 ? 2 : nd, nb < 0 ? 0 : nb > 2 ? 2 : nb);
-            };
-            auto MEMW = [&](auto set_tag, int x) {                          // MEM(x) with set = x % 3: A fragments from LDS, B(x+2) -> set (x+2) % 3
-                constexpr int SET = decltype(set_tag)::value;
-                const uint32_t sa = a_b + (x & 3) * SLOT;
-                fa[0][0] = blk_lds_read128<0>(sa);
-                if constexpr (MIW > 1) fa[1][0] = blk_lds_read128<2048>(sa);
-                if constexpr (MIW > 2) fa[2][0] = blk_lds_read128<4096>(sa);
-                if constexpr (MIW > 3) fa[3][0] = blk_lds_read128<6144>(sa);
-                if constexpr (MIW > 4) fa[4][0] = blk_lds_read128<8192>(sa);
-                fa[0][1] = blk_lds_read128<1024>(sa);
-                if constexpr (MIW > 1) fa[1][1] = blk_lds_read128<2048 + 1024>(sa);
-                if constexpr (MIW > 2) fa[2][1] = blk_lds_read128<4096 + 1024>(sa);
-                if constexpr (MIW > 3) fa[3][1] = blk_lds_read128<6144 + 1024>(sa);
-                if constexpr (MIW > 4) fa[4][1] = blk_lds_read128<8192 + 1024>(sa);
-                if (x + 2 < H) loadB(std::integral_constant<int, (SET + 2) % 3>{}, x + 2);
-                if (x + 3 < H) hstage(x + 3);
-                wait_wd(x);
-                blk_wait_lgkmcnt<0>();
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            auto MFMAW = [&](auto set_tag) {
-                constexpr int SET = decltype(set_tag)::value;
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (X3) {
-#pragma unroll
-                    for (int t = 0; t < 3; ++t)
-#pragma unroll
-                        for (int i = 0; i < MIW; ++i)
-#pragma unroll
-                            for (int j = 0; j < NJ; ++j)
-                                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fbq[SET][j][t == 1 ? 1 : 0], fa[i][t == 0 ? 1 : 0], acc[i][j], 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                        for (int i = 0; i < MIW; ++i)
-#pragma unroll
-                            for (int j = 0; j < NJ; ++j)
-                                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fbq[SET][j][kk], fa[i][kk], acc[i][j], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            auto body = [&](auto set_tag, int k) {                          // slot k: group 0: MFMA(k), MEM(k+1);  group 1: MEM(k+1), MFMA(k+1)
-                constexpr int SET = decltype(set_tag)::value;
-                using next = std::integral_constant<int, (SET + 1) % 3>;
-                __builtin_amdgcn_s_barrier();
-                if (wm == 0) MFMAW(set_tag);
-                if (k + 1 < H) {
-                    MEMW(next{}, k + 1);
-                    if (wm == 1) MFMAW(next{});
-                }
-            };
-            // prologue in the steady-state issue order: DMA(0) | B(0) DMA(1) | B(1) DMA(2); then DMA(0) must have landed (barrier: everyone's share)
-            hstage(0);
-            loadB(std::integral_constant<int, 0>{}, 0);
-            if (H > 1) { hstage(1); loadB(std::integral_constant<int, 1>{}, 1); }
-            if (H > 2) hstage(2);
-            wait_young(H > 2 ? 2 : H - 1, H > 1 ? 2 : 1);
+        MEM(0);
+        if (wm == 1) MFMA();                                           // group 1 is half a slot ahead
+        for (int k = 0; k < H; ++k) {
             __builtin_amdgcn_s_barrier();
-            MEMW(std::integral_constant<int, 0>{}, 0);
-            if (wm == 1) MFMAW(std::integral_constant<int, 0>{});
-            for (int k = 0; k < H; k += 3) {
-                body(std::integral_constant<int, 0>{}, k);
-                if (k + 1 < H) body(std::integral_constant<int, 1>{}, k + 1);
-                if (k + 2 < H) body(std::integral_constant<int, 2>{}, k + 2);
+            if (wm == 0) MFMA();                                       // MFMA(k)
+            if (k + 1 < H) {
+                MEM(k + 1);
+                if (wm == 1) MFMA();                                   // MFMA(k + 1)
             }
-        } else if constexpr (SCHED == 1) {
-            MEM(0);
-            if (wm == 1) MFMA();                                           // group 1 is half a slot ahead
-            for (int k = 0; k < H; ++k) {
-                __builtin_amdgcn_s_barrier();
-                if (wm == 0) MFMA();                                       // MFMA(k)
-                if (k + 1 < H) {
-                    MEM(k + 1);
-                    if (wm == 1) MFMA();                                   // MFMA(k + 1)
-                }
-            }
-        } else {
-            // two barriers per half tile: MEM(h) of one group beside MFMA(h) of the other, rendezvous after each; group 1 one barrier behind
-            if (wm == 1) __builtin_amdgcn_s_barrier();
-            for (int h = 0; h < H; ++h) {
-                MEM(h);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_s_setprio(1);
-                MFMA();
-                __builtin_amdgcn_s_setprio(0);
-                __builtin_amdgcn_s_barrier();
-            }
-            if (wm == 0) __builtin_amdgcn_s_barrier();
         }
     };
     if constexpr (MI0 == MI1) {
@@ -368,14 +199,9 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
                     // plain: acc + bias;  folded LayerNorm: rstd * acc + (bias' - rstd * mean * colsum)   (rs = 1, rm = 0, cq = 0 when not folded)
                     f32x2_t v0 = {fmaf(acc[i][j][4 * q], rs[i], fmaf(-rm[i], cq[q].x, bq[q].x)), fmaf(acc[i][j][4 * q + 1], rs[i], fmaf(-rm[i], cq[q].y, bq[q].y))};
                     f32x2_t v1 = {fmaf(acc[i][j][4 * q + 2], rs[i], fmaf(-rm[i], cq[q].z, bq[q].z)), fmaf(acc[i][j][4 * q + 3], rs[i], fmaf(-rm[i], cq[q].w, bq[q].w))};
-                    if constexpr (X3) {
-                        // parity-grade epilogue: erf GELU like nn.GELU (vit.py:66-68; gelu_as: 8.7e-7 from float64, the fp32 framework GELU 1.2e-6), result split into hi / lo
-                        if constexpr (EPI == 1) { v0.x = gelu_as(v0.x); v0.y = gelu_as(v0.y); v1.x = gelu_as(v1.x); v1.y = gelu_as(v1.y); }
-                        split_bf16x2(v0.x, v0.y, pk[q][0], pl[q][0]); split_bf16x2(v1.x, v1.y, pk[q][1], pl[q][1]);
-                    } else {
-                        if constexpr (EPI == 1) { v0 = gelu_fast2(v0); v1 = gelu_fast2(v1); }
-                        pk[q][0] = pack_bf16x2(v0.x, v0.y); pk[q][1] = pack_bf16x2(v1.x, v1.y);
-                    }
+                    // parity-grade epilogue: erf GELU like nn.GELU (vit.py:66-68; gelu_as: 8.7e-7 from float64, the fp32 framework GELU 1.2e-6), result split into hi / lo
+                    if constexpr (EPI == 1) { v0.x = gelu_as(v0.x); v0.y = gelu_as(v0.y); v1.x = gelu_as(v1.x); v1.y = gelu_as(v1.y); }
+                    split_bf16x2(v0.x, v0.y, pk[q][0], pl[q][0]); split_bf16x2(v1.x, v1.y, pk[q][1], pl[q][1]);
                 }
                 const size_t roff = ((size_t)(rb0 + i) * NC8 + ((nb0 + j * 32) >> 3)) * 512 + l31 * 16;
                 char* rowp = (char*)p.C + roff;
@@ -386,14 +212,12 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
                     const auto r1 = __builtin_amdgcn_permlane32_swap(pk[q][1], pk[q + 1][1], false, false);
                     *(uint4*)(rowp + (q + hi) * 512) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
                 }
-                if constexpr (X3) {
-                    char* rowl = (char*)p.C_lo + roff;
+                char* rowl = (char*)p.C_lo + roff;
 #pragma unroll
-                    for (int q = 0; q < 4; q += 2) {
-                        const auto r0 = __builtin_amdgcn_permlane32_swap(pl[q][0], pl[q + 1][0], false, false);
-                        const auto r1 = __builtin_amdgcn_permlane32_swap(pl[q][1], pl[q + 1][1], false, false);
-                        *(uint4*)(rowl + (q + hi) * 512) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-                    }
+                for (int q = 0; q < 4; q += 2) {
+                    const auto r0 = __builtin_amdgcn_permlane32_swap(pl[q][0], pl[q + 1][0], false, false);
+                    const auto r1 = __builtin_amdgcn_permlane32_swap(pl[q][1], pl[q + 1][1], false, false);
+                    *(uint4*)(rowl + (q + hi) * 512) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
                 }
             }
         }
@@ -455,8 +279,7 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
                         o.x -= sh[i]; o.y -= sh[i]; o.z -= sh[i]; o.w -= sh[i];
                         sx[i] += o.x; sx[i] += o.y; sx[i] += o.z; sx[i] += o.w;
                         sxx[i] = fmaf(o.x, o.x, sxx[i]); sxx[i] = fmaf(o.y, o.y, sxx[i]); sxx[i] = fmaf(o.z, o.z, sxx[i]); sxx[i] = fmaf(o.w, o.w, sxx[i]);
-                        if constexpr (X3) { split_bf16x2(o.x, o.y, pk[q][0], pl[q][0]); split_bf16x2(o.z, o.w, pk[q][1], pl[q][1]); }
-                        else { pk[q][0] = pack_bf16x2(o.x, o.y); pk[q][1] = pack_bf16x2(o.z, o.w); }
+                        split_bf16x2(o.x, o.y, pk[q][0], pl[q][0]); split_bf16x2(o.z, o.w, pk[q][1], pl[q][1]);
                     }
                 }
                 if (emit) {
@@ -468,14 +291,12 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
                         const auto r1 = __builtin_amdgcn_permlane32_swap(pk[q][1], pk[q + 1][1], false, false);
                         *(uint4*)(rowp + (q + hi) * 512) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
                     }
-                    if constexpr (X3) {                                     // the centred row as an operand PAIR (bf16x3 fold)
-                        char* rowl = (char*)p.xhat_lo + xoff;
+                    char* rowl = (char*)p.xhat_lo + xoff;                       // the centred row as an operand PAIR (bf16x3 fold)
 #pragma unroll
-                        for (int q = 0; q < 4; q += 2) {
-                            const auto r0 = __builtin_amdgcn_permlane32_swap(pl[q][0], pl[q + 1][0], false, false);
-                            const auto r1 = __builtin_amdgcn_permlane32_swap(pl[q][1], pl[q + 1][1], false, false);
-                            *(uint4*)(rowl + (q + hi) * 512) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-                        }
+                    for (int q = 0; q < 4; q += 2) {
+                        const auto r0 = __builtin_amdgcn_permlane32_swap(pl[q][0], pl[q + 1][0], false, false);
+                        const auto r1 = __builtin_amdgcn_permlane32_swap(pl[q][1], pl[q + 1][1], false, false);
+                        *(uint4*)(rowl + (q + hi) * 512) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
                     }
                 }
             }
@@ -501,10 +322,10 @@ __global__ __launch_bounds__(512, 2) void gemm_blk_kernel(const whmr_gemm_blk_de
     }
 }
 
-template <int MI0, int MI1, int EPI, int SCHED, bool X3, bool WD = false>
-static int launch_blk_s(const whmr_gemm_blk_desc& p, hipStream_t st) {
-    using cfg = blk_cfg<MI0, MI1, WD>;
-    auto kern = gemm_blk_kernel<MI0, MI1, EPI, SCHED, X3, WD>;
+template <int MI0, int MI1, int EPI>
+static int launch_blk(const whmr_gemm_blk_desc& p, hipStream_t st) {
+    using cfg = blk_cfg<MI0, MI1>;
+    auto kern = gemm_blk_kernel<MI0, MI1, EPI>;
     static bool attr_done = false;
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, cfg::LDS);
@@ -517,42 +338,8 @@ static int launch_blk_s(const whmr_gemm_blk_desc& p, hipStream_t st) {
     return 0;
 }
 
-template <int MI0, int MI1, int EPI, bool X3>
-static int launch_blk(const whmr_gemm_blk_desc& p, hipStream_t st, int sched) {
-    // Only the split-bf16 form (X3) with W through LDS and the one-barrier schedule is compiled since round 5.  The body still carries its plain-bf16
-    // branch (the bf16 kernel moved to 16x16x32: gemm_blk16_impl.h), the two-barrier schedule and the W-direct main loop (measured 3-4 % slower,
-    // DESIGN 6) behind `if constexpr`; none of them is instantiated.
-    static_assert(X3, "the 32x32x16 blocked kernel is the split-bf16 kernel");
-    (void)sched;
-    return launch_blk_s<MI0, MI1, EPI, 1, true>(p, st);
+static int blk_launch_tile(const whmr_gemm_blk_desc& p, int tile, hipStream_t st) {
+    return blk_dispatch_tile(tile, [&](auto mi0, auto mi1) {
+        return blk_dispatch_epi(p.epi, [&](auto epi) { return launch_blk<decltype(mi0)::value, decltype(mi1)::value, decltype(epi)::value>(p, st); });
+    });
 }
-
-template <int MI0, int MI1, bool X3>
-static int launch_blk_epi(const whmr_gemm_blk_desc& p, hipStream_t st, int sched) {
-    switch (p.epi) {
-        case 0: return launch_blk<MI0, MI1, 0, X3>(p, st, sched);
-        case 1: return launch_blk<MI0, MI1, 1, X3>(p, st, sched);
-        case 2: return launch_blk<MI0, MI1, 2, X3>(p, st, sched);
-        case 3: return launch_blk<MI0, MI1, 3, X3>(p, st, sched);
-    }
-    return (int)hipErrorInvalidValue;
-}
-
-// Tile heights (x 256 columns): the wave rows own MI0 and MI1 row blocks.
-template <bool X3>
-static int blk_launch_tile(const whmr_gemm_blk_desc& p, int tile, hipStream_t st, int sched) {
-    switch (tile) {
-        case 0x44: return launch_blk_epi<4, 4, X3>(p, st, sched);      // 256 x 256
-        case 0x55: return launch_blk_epi<5, 5, X3>(p, st, sched);      // 320 x 256
-        case 0x43: return launch_blk_epi<4, 3, X3>(p, st, sched);      // 224 x 256
-        case 0x33: return launch_blk_epi<3, 3, X3>(p, st, sched);      // 192 x 256
-        case 0x32: return launch_blk_epi<3, 2, X3>(p, st, sched);      // 160 x 256
-        case 0x22: return launch_blk_epi<2, 2, X3>(p, st, sched);      // 128 x 256
-        case 0x54: return launch_blk_epi<5, 4, X3>(p, st, sched);      // 288 x 256
-        case 0x21: return launch_blk_epi<2, 1, X3>(p, st, sched);      // 96 x 256: ViT-L at 32 crops (6144 tokens) x N = 1024 is exactly 256 such tiles
-    }
-    return (int)hipErrorInvalidValue;
-}
-
-// split-operand launcher (gemm_blk_x3.hip; library-internal), reached through whmr_gemm_blk / whmr_gemm_blk_tile when the descriptor carries lo halves
-__attribute__((visibility("hidden"))) int blk_x3_launch_tile(const whmr_gemm_blk_desc* pp, int tile, void* stream, int sched);

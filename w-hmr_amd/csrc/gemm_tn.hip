@@ -84,7 +84,7 @@ struct tn_params {
     const bf16_t* zeros;      // >= 512 B of zeros
 };
 
-// PP (round 4): the two wave rows are two GROUPS half a step apart (the blocked forward kernel's schedule, gemm_blk16_impl.h SCHED 1): per 32-row step a
+// PP (round 4): the two wave rows are two GROUPS half a step apart (the blocked forward kernel's schedule, gemm_blk16_impl.h): per 32-row step a
 // group runs MEM (all fragment reads of the step + its share of the DMA two steps ahead + the counted wait) and MFMA (16 MFMAs from registers), with
 // ONE barrier per step; group 0 walks a step as [MFMA | MEM], group 1 as [MEM | MFMA], so on every SIMD one wave feeds the matrix pipe while its
 // partner waits for LDS.  In the lock-step loop (PP = false) both waves of a SIMD issue their fragment reads at the same time and the pipe idles
