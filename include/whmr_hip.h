@@ -577,6 +577,59 @@ int whmr_iuv_losses(const void* y, int y_bf16, long ld, const float* iuv, long s
 int whmr_iuv_losses_bwd(const void* y, int y_bf16, long ld, const float* iuv, long sb, long sc, long sh, long sw, int B, int H, int W,
                         float point_weight, const float* g, void* dy, long ldg, void* stream);
 
+/* ---- the training objective on preds_dict['smpl_out'][1..3] (core/trainer.py:498-609; csrc/whmr_loss.hip): three launches, no atomics (repeated calls
+ * are bit-identical), no allocation and no host read (graph-capturable: the valid counts of the masked terms are summed on the device).
+ * Terms of one stage, in the order of losses[stage * WHMR_LOSS_TERMS + k] (stage s = smpl_out[s + 1], key suffix _{s+1}):
+ *   0 loss_regr_pose      w_pose  * mean over has_smpl samples of (rotmat - R(gt_pose))^2, 24 * 9 entries      (trainer.py:242-253,538-539)
+ *   1 loss_regr_betas     w_shape * the same masked mean of (shape - gt_betas)^2, 10 entries                   (:242-253,540)
+ *   2 loss_keypoints_3d   w_kp3d  * mean over has_pose_3d samples, 24 joints x 3, of conf (p^ - g^)^2: p = kp_3d rows 25..48, g = pose_3d[..., :3],
+ *                         conf = pose_3d[..., 3], each centred on the mean of its joints 2 and 3               (:214-231,572)
+ *   3 loss_shape, 4 loss_shape_sub, 5 loss_shape_temp   w_vert * L1 mean over has_smpl samples of verts / sub_verts / temp_verts   (:233-240,576-582)
+ *   6 loss_cam            mean of exp(-10 cam[:, 0])^2                                                          (:586)
+ *   7 loss_keypoints      w_kp2d * mean over B * 49 * 2 of conf (kp_2d - gt)^2, conf = gt[..., 2] * (row < 25 ? w_openpose : w_gt)   (:203-212,544-549)
+ *   8 loss_keypoints_world  the same on kp_2d_w / gt_kp_2d_w, x and y times orig_shape[:, 1] / bbox_width and orig_shape[:, 0] / bbox_height   (:501-506,551-564)
+ *   9 loss_focal_length   w_focal * mean of (focal - gt_focal)^2                                                (:566-569)
+ * A null prediction pointer switches its term off (losses entry 0.0); a masked term without a valid sample is exactly 0.0 and so is its gradient.
+ * Everything is contiguous fp32 (shape and cam may be column slices of a wider row); has_smpl / has_pose_3d / orig_shape hold their flags and sizes as fp32. */
+#define WHMR_LOSS_STAGES 3
+#define WHMR_LOSS_TERMS 10
+struct whmr_loss_stage {            /* one stage's predictions (read), or where the backward writes their gradients; term k reads field k */
+    float* rotmat;                  /* [B, 24, 3, 3] */
+    float* shape;                   /* [B, 10]      theta[:, 3:13]: rows shape_stride floats apart */
+    float* kp_3d;                   /* [B, 49, 3] */
+    float* verts;                   /* [B, V, 3] */
+    float* sub_verts;               /* [B, V_sub, 3] */
+    float* temp_verts;              /* [B, V_temp, 3] */
+    float* cam;                     /* [B, 3]       theta[:, :3]: rows cam_stride floats apart; the gradient's columns 1, 2 are zero */
+    float* kp_2d;                   /* [B, 49, 2] */
+    float* kp_2d_w;                 /* [B, 49, 2] */
+    float* focal;                   /* [B] */
+    int64_t shape_stride, cam_stride;   /* predictions only (column slices of theta are read in place); gradients are dense [B, 10] / [B, 3] */
+};
+struct whmr_loss_args {
+    struct whmr_loss_stage pred[WHMR_LOSS_STAGES];
+    struct whmr_loss_stage grad[WHMR_LOSS_STAGES];      /* backward only: written for every non-null pred (kp_3d rows 0..24 get zero) */
+    const float* gt_pose;           /* [B, 72] axis-angle: R = batch_rodrigues (utils/geometry.py:14-51) is evaluated in the kernel */
+    const float* gt_betas;          /* [B, 10] */
+    const float* pose_3d;           /* [B, 24, 4] */
+    const float* has_smpl;          /* [B] 0 / 1 */
+    const float* has_pose_3d;       /* [B] 0 / 1 */
+    const float* gt_verts; const float* gt_sub_verts; const float* gt_temp_verts;   /* [B, V | V_sub | V_temp, 3] */
+    const float* gt_kp_2d; const float* gt_kp_2d_w;     /* [B, 49, 3] = (x, y, conf) */
+    const float* orig_shape;        /* [B, 2] = (height, width) */
+    const float* bbox_width; const float* bbox_height;  /* [B] */
+    const float* gt_focal;          /* [B] */
+    int32_t B, V, V_sub, V_temp;
+    float w_pose, w_shape, w_kp3d, w_vert, w_kp2d, w_focal;   /* cfg.LOSS.POSE_W, SHAPE_W, KP_3D_W, VERT_W, KP_2D_W, FOCAL_WEIGHTS */
+    float w_openpose, w_gt;         /* options.openpose_train_weight, options.gt_train_weight */
+};
+/* partial: >= the floats whmr_train_losses_workspace reports (one per workgroup of the first launch, fully rewritten by every call);
+ * losses [WHMR_LOSS_STAGES * WHMR_LOSS_TERMS]; counts [2] = (sum has_smpl, sum has_pose_3d), kept for the backward. */
+int whmr_train_losses_workspace(const struct whmr_loss_args* a, long* n_floats);
+int whmr_train_losses(const struct whmr_loss_args* a, float* partial, float* losses, float* counts, void* stream);
+/* a->grad = d(sum_k g[k] losses[k]) / d(a->pred), one elementwise launch; g [WHMR_LOSS_STAGES * WHMR_LOSS_TERMS] and counts [2] on the device. */
+int whmr_train_losses_bwd(const struct whmr_loss_args* a, const float* counts, const float* g, void* stream);
+
 /* ---- output side of the demo: mesh overlay renderer (csrc/mesh_render.hip) = render_overlay_image (utils/renderer_cam.py:41-141: pyrender scene,
  * IntrinsicsCamera, OffscreenRenderer, valid-mask composite) as render_image_group (:144-225) calls it per person from demo/tester.py:176-214.
  * verts [P, V, 3] fp32; faces [F, 3] int32 (indices in [0, V): the caller checks); vf_ptr [V + 1] / vf_idx [3 F] int32: vertex -> face CSR of the

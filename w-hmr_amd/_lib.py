@@ -86,6 +86,24 @@ class WhmrTnItem(C.Structure):
                 ('db', C.c_void_p), ('Mo', C.c_int32), ('No', C.c_int32)]
 
 
+LOSS_STAGES, LOSS_TERMS = 3, 10             # WHMR_LOSS_STAGES, WHMR_LOSS_TERMS (include/whmr_hip.h)
+LOSS_FIELDS = ('rotmat', 'shape', 'kp_3d', 'verts', 'sub_verts', 'temp_verts', 'cam', 'kp_2d', 'kp_2d_w', 'focal')
+
+
+class _WhmrLossStage(C.Structure):
+    """struct whmr_loss_stage (include/whmr_hip.h): one stage's predictions, or their gradients; field k belongs to term k"""
+    _fields_ = [(k, C.c_void_p) for k in LOSS_FIELDS] + [('shape_stride', C.c_int64), ('cam_stride', C.c_int64)]
+
+
+class _WhmrLossArgs(C.Structure):
+    """struct whmr_loss_args (include/whmr_hip.h): the training objective on smpl_out[1..3] (csrc/whmr_loss.hip)"""
+    _fields_ = ([('pred', _WhmrLossStage * LOSS_STAGES), ('grad', _WhmrLossStage * LOSS_STAGES)]
+                + [(k, C.c_void_p) for k in ('gt_pose', 'gt_betas', 'pose_3d', 'has_smpl', 'has_pose_3d', 'gt_verts', 'gt_sub_verts', 'gt_temp_verts',
+                                             'gt_kp_2d', 'gt_kp_2d_w', 'orig_shape', 'bbox_width', 'bbox_height', 'gt_focal')]
+                + [(k, C.c_int32) for k in ('B', 'V', 'V_sub', 'V_temp')]
+                + [(k, C.c_float) for k in ('w_pose', 'w_shape', 'w_kp3d', 'w_vert', 'w_kp2d', 'w_focal', 'w_openpose', 'w_gt')])
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_long
 _SIGS = {
     'whmr_gemm_bf16': [C.POINTER(WhmrGemm), _I, _P],
@@ -191,6 +209,9 @@ _SIGS = {
                          _P, _P],
     'whmr_iuv_losses': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     'whmr_iuv_losses_bwd': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _L, _P],
+    'whmr_train_losses_workspace': [C.POINTER(_WhmrLossArgs), C.POINTER(C.c_long)],
+    'whmr_train_losses': [C.POINTER(_WhmrLossArgs), _P, _P, _P, _P],
+    'whmr_train_losses_bwd': [C.POINTER(_WhmrLossArgs), _P, _P, _P],
     'whmr_weights_prepare': [_P, _I, _I, _P],
     'whmr_augment_crop': [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     'whmr_augment_labels': [_P, _I, C.POINTER(_WhmrAugmentLabelsIO), _P],
@@ -836,6 +857,85 @@ def iuv_losses_bwd(y, iuv, point_weight, g, ldg):
     dy = torch.empty(P, ldg, dtype=y.dtype, device=y.device)
     _check(lib().whmr_iuv_losses_bwd(*a, float(point_weight), g.data_ptr(), dy.data_ptr(), ldg, _stream()), 'whmr_iuv_losses_bwd')
     return dy
+
+
+# ---- the training objective (whmr_loss.hip) --------------------------------------------------------------------------------
+LOSS_TARGETS = ('gt_pose', 'gt_betas', 'pose_3d', 'has_smpl', 'has_pose_3d', 'gt_verts', 'gt_sub_verts', 'gt_temp_verts', 'gt_kp_2d', 'gt_kp_2d_w',
+                'orig_shape', 'bbox_width', 'bbox_height', 'gt_focal')
+LOSS_WEIGHTS = ('w_pose', 'w_shape', 'w_kp3d', 'w_vert', 'w_kp2d', 'w_focal', 'w_openpose', 'w_gt')
+
+
+def _loss_args(preds, targets, weights, grads=None):
+    """preds: LOSS_STAGES dicts {field of LOSS_FIELDS: [B, ...] tensor or None (term off)}; targets: {name of LOSS_TARGETS: tensor or None};
+    weights: {name of LOSS_WEIGHTS: float}.  Every shape the kernels index by is checked here: they check none."""
+    B = targets['gt_pose'].shape[0]
+    a = _WhmrLossArgs()
+    a.B = B
+    mesh = {'verts': 'V', 'sub_verts': 'V_sub', 'temp_verts': 'V_temp'}
+    want = {'gt_pose': (B, 72), 'gt_betas': (B, 10), 'pose_3d': (B, 24, 4), 'has_smpl': (B,), 'has_pose_3d': (B,), 'gt_kp_2d': (B, 49, 3),
+            'gt_kp_2d_w': (B, 49, 3), 'orig_shape': (B, 2), 'bbox_width': (B,), 'bbox_height': (B,), 'gt_focal': (B,)}
+    for k, n in mesh.items():
+        t = targets.get('gt_' + k)
+        if t is not None:
+            assert t.dim() == 3 and t.shape[0] == B and t.shape[2] == 3, (k, tuple(t.shape))
+            setattr(a, n, t.shape[1])
+            want['gt_' + k] = tuple(t.shape)
+    for k in LOSS_TARGETS:
+        t = targets.get(k)
+        if t is not None:
+            _dev(t)
+            assert tuple(_f32c(t).shape) == want[k], (k, tuple(t.shape), want[k])
+            setattr(a, k, t.data_ptr())
+    shapes = {'rotmat': (B, 24, 3, 3), 'shape': (B, 10), 'kp_3d': (B, 49, 3), 'cam': (B, 3), 'kp_2d': (B, 49, 2), 'kp_2d_w': (B, 49, 2), 'focal': (B,)}
+    needs = {'kp_2d': ('gt_kp_2d',), 'kp_2d_w': ('gt_kp_2d_w', 'orig_shape', 'bbox_width', 'bbox_height'), 'focal': ('gt_focal',)}
+    assert len(preds) == LOSS_STAGES
+    for s, d in enumerate(preds):
+        for k in LOSS_FIELDS:
+            t = d.get(k)
+            if t is None:
+                continue
+            _dev(t)
+            shp = want.get('gt_' + k) if k in mesh else shapes[k]
+            assert shp is not None and tuple(t.shape) == shp and t.dtype == torch.float32, (s, k, tuple(t.shape), shp, t.dtype)
+            if k in ('shape', 'cam'):                    # column slices of theta / of the regressor's state are read in place
+                assert t.stride(1) == 1 and t.stride(0) >= t.shape[1], (k, t.stride())
+                setattr(a.pred[s], k + '_stride', t.stride(0))
+            else:
+                _f32c(t)
+            assert all(targets.get(n) is not None for n in needs.get(k, ())), (k, 'needs', needs.get(k))
+            setattr(a.pred[s], k, t.data_ptr())
+            if grads is not None:
+                g = grads[s][k]
+                assert g.is_cuda and _f32c(g).shape == t.shape
+                setattr(a.grad[s], k, g.data_ptr())
+    for k in LOSS_WEIGHTS:
+        setattr(a, k, float(weights[k]))
+    return a
+
+
+def train_losses(preds, targets, weights):
+    """-> (losses [LOSS_STAGES * LOSS_TERMS], counts [2]): the terms of core/trainer.py:498-609 in the order include/whmr_hip.h documents
+    (whmr_train_losses); counts = the valid samples of the masked terms, kept on the device for the backward."""
+    a = _loss_args(preds, targets, weights)
+    dev = targets['gt_pose'].device
+    n = C.c_long()
+    _check(lib().whmr_train_losses_workspace(C.byref(a), C.byref(n)), 'whmr_train_losses_workspace')
+    partial = torch.empty(n.value, dtype=torch.float32, device=dev)
+    out = torch.empty(LOSS_STAGES * LOSS_TERMS + 2, dtype=torch.float32, device=dev)
+    losses, counts = out[:LOSS_STAGES * LOSS_TERMS], out[LOSS_STAGES * LOSS_TERMS:]
+    _check(lib().whmr_train_losses(C.byref(a), partial.data_ptr(), losses.data_ptr(), counts.data_ptr(), _stream()), 'whmr_train_losses')
+    return losses, counts
+
+
+def train_losses_bwd(preds, targets, weights, counts, g):
+    """d(sum_k g[k] losses[k]) / d(every tensor of preds) -> LOSS_STAGES dicts of the same keys (whmr_train_losses_bwd: one launch)"""
+    _dev(g, counts)
+    g = _f32c(g.contiguous())
+    assert g.numel() == LOSS_STAGES * LOSS_TERMS and counts.numel() == 2
+    grads = [{k: torch.empty_like(t) for k, t in d.items() if t is not None} for d in preds]
+    a = _loss_args(preds, targets, weights, grads)
+    _check(lib().whmr_train_losses_bwd(C.byref(a), counts.data_ptr(), g.data_ptr(), _stream()), 'whmr_train_losses_bwd')
+    return grads
 
 
 def layernorm(x, weight, bias, out, eps):
