@@ -368,6 +368,30 @@ int whmr_colsum(const void* x, int is_bf16, long ld, int R, int C, float* out, i
  * ceil(K/64); total_tiles = their sum.  Same bits as whmr_cast_bf16 / whmr_transpose_cast. */
 struct whmr_wprep_item { const float* src; void* dst; void* dst_t; int32_t N, K, tile_begin, tiles_k; };
 int whmr_weights_prepare(const void* items, int n_items, int total_tiles, void* stream);
+/* Adam step over ALL parameters of a model in two launches (csrc/adam.hip; torch's non-amsgrad Adam with L2 weight decay, core/trainer.py:615),
+ * driven by a DEVICE-resident table so that a captured graph replays it.  hyper: one row per parameter group (struct whmr_adam_hyper), read on the device by every launch
+ * (a learning rate changed between two replays is followed).  Item = one parameter: p, g, m (exp_avg), v (exp_avg_sq) fp32 of numel elements
+ * (4-byte alignment is enough: 16-byte accesses are used only where all four pointers allow them), step = its step count (fp32 device
+ * scalar), group = its row of hyper, bc1 / bc2 = the bias corrections 1 - beta^step (written by the advance launch, read by the step launch).
+ * tiles_k == 0: a "flat" item of ceil(numel / WHMR_ADAM_CHUNK) workgroups.  tiles_k > 0: a "tile" item, p is a matrix [N, K] (nn.Linear layout) of
+ * ceil(N/64) * tiles_k 64x64 tiles, tiles_k = ceil(K/64), whose update also writes bf16(p_new) to w [N, K] and wt [K, N] (either may be null): the
+ * operand copies whmr_weights_prepare makes, same bits, without the second pass over the weights.  items are sorted by block_begin (the item's
+ * first workgroup); total_blocks = the sum of their workgroups.
+ *   g' = g + wd p;  m += (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g'^2;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)     (all fp32) */
+#define WHMR_ADAM_CHUNK 4096
+struct whmr_adam_hyper { double beta1, beta2, lr; float eps, weight_decay; };   /* doubles: 1 - beta and 1 - beta^step lose 4 digits from an fp32 beta, and lr / bc1 is
+                                                                                  * formed in double and rounded once, as torch forms it on the host */
+struct whmr_adam_item {
+    float* p; const float* g; float* m; float* v; float* step;
+    void* w; void* wt;
+    int64_t numel;
+    int32_t N, K, block_begin, tiles_k, group, reserved;
+    double bc1, bc2;
+};
+/* one thread per item: step += 1, bc1 = 1 - beta1^step, bc2 = 1 - beta2^step (evaluated in double) */
+int whmr_adam_advance(void* items, int n_items, const void* hyper, void* stream);
+/* the update itself: one launch of total_blocks workgroups; run whmr_adam_advance first */
+int whmr_adam_step(const void* items, int n_items, int total_blocks, const void* hyper, void* stream);
 /* LayerNorm backward: dx = dLN(x; gamma)(dy) + dres (dres nullable, dx may alias it); dgamma/dbeta (+)=; scratch >= 2048*C floats.
  * cast_out (nullable) [rows, C] bf16 = dx * row_scale[row] (row_scale nullable): the operand of the next branch's backward GEMMs, stochastic-depth
  * factor included (vit.py:132-139), written by the same pass. */

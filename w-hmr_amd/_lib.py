@@ -104,6 +104,21 @@ class _WhmrLossArgs(C.Structure):
                 + [(k, C.c_float) for k in ('w_pose', 'w_shape', 'w_kp3d', 'w_vert', 'w_kp2d', 'w_focal', 'w_openpose', 'w_gt')])
 
 
+ADAM_CHUNK = 4096                           # WHMR_ADAM_CHUNK (include/whmr_hip.h): elements per workgroup of a flat item
+
+
+class _WhmrAdamHyper(C.Structure):
+    """struct whmr_adam_hyper (include/whmr_hip.h): one parameter group's row of the device-resident hyper-parameters"""
+    _fields_ = [('beta1', C.c_double), ('beta2', C.c_double), ('lr', C.c_double), ('eps', C.c_float), ('weight_decay', C.c_float)]
+
+
+class _WhmrAdamItem(C.Structure):
+    """struct whmr_adam_item (include/whmr_hip.h): one parameter of the fused Adam step (csrc/adam.hip)"""
+    _fields_ = ([(k, C.c_void_p) for k in ('p', 'g', 'm', 'v', 'step', 'w', 'wt')] + [('numel', C.c_int64)]
+                + [(k, C.c_int32) for k in ('N', 'K', 'block_begin', 'tiles_k', 'group', 'reserved')]
+                + [('bc1', C.c_double), ('bc2', C.c_double)])
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_long
 _SIGS = {
     'whmr_gemm_bf16': [C.POINTER(WhmrGemm), _I, _P],
@@ -213,6 +228,8 @@ _SIGS = {
     'whmr_train_losses': [C.POINTER(_WhmrLossArgs), _P, _P, _P, _P],
     'whmr_train_losses_bwd': [C.POINTER(_WhmrLossArgs), _P, _P, _P],
     'whmr_weights_prepare': [_P, _I, _I, _P],
+    'whmr_adam_advance': [_P, _I, _P, _P],
+    'whmr_adam_step': [_P, _I, _I, _P, _P],
     'whmr_augment_crop': [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     'whmr_augment_labels': [_P, _I, C.POINTER(_WhmrAugmentLabelsIO), _P],
     'whmr_maxpool_nhwc': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -1483,6 +1500,26 @@ class WeightOperands:
             _check(lib().whmr_weights_prepare(self.table.data_ptr(), len(self.params), self.total, _stream()), 'whmr_weights_prepare')
             self.versions = v
         return self.copies
+
+    def mark_current(self):
+        """the copies were just written by someone else from the parameters' present values (train.FusedAdam's tile items): refresh() launches nothing
+        until a version moves again"""
+        self.versions = [p._version for p in self.params]
+
+
+def adam_advance(items, n_items, hyper):
+    """items: uint8 device tensor of n_items struct whmr_adam_item, hyper: uint8 device tensor of struct whmr_adam_hyper rows (one per group):
+    step += 1 and the bias corrections of every item (csrc/adam.hip)"""
+    _dev(items, hyper)
+    assert items.dtype == torch.uint8 and items.numel() >= n_items * C.sizeof(_WhmrAdamItem) and hyper.dtype == torch.uint8
+    _check(lib().whmr_adam_advance(items.data_ptr(), n_items, hyper.data_ptr(), _stream()), 'whmr_adam_advance')
+
+
+def adam_step(items, n_items, total_blocks, hyper):
+    """the Adam update of every item of the table in one launch; tile items also write their bf16 W / W^T operand copies"""
+    _dev(items, hyper)
+    assert items.dtype == torch.uint8 and items.numel() >= n_items * C.sizeof(_WhmrAdamItem) and hyper.dtype == torch.uint8
+    _check(lib().whmr_adam_step(items.data_ptr(), n_items, total_blocks, hyper.data_ptr(), _stream()), 'whmr_adam_step')
 
 
 def layernorm_bwd(x, dy, gamma, dres, dx, dgamma, dbeta, eps, accumulate=False, cast_out=None, row_scale=None):
