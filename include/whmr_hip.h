@@ -392,6 +392,25 @@ struct whmr_adam_item {
 int whmr_adam_advance(void* items, int n_items, const void* hyper, void* stream);
 /* the update itself: one launch of total_blocks workgroups; run whmr_adam_advance first */
 int whmr_adam_step(const void* items, int n_items, int total_blocks, const void* hyper, void* stream);
+/* Gradient guard of the Adam step (optional; a guarded step is the three launches below INSTEAD of the two above, same table, capturable):
+ * the global L2 norm of the table's gradients, clipping by it, and skipping the whole step when it is not finite.
+ * cfg: host-pushed row.  max_norm <= 0: no clipping.  skip_nonfinite != 0: a NaN / Inf norm leaves p, m, v, step, bc1 / bc2 and w / wt untouched.
+ * state: device-written.  grad_norm = sqrt(sum g^2) before clipping; clip_coef = min(1, max_norm / (grad_norm + 1e-6)), 1 when not clipping, 0 on
+ * a skipped step; apply = 0 on a skipped step; steps_seen / steps_skipped accumulate (zero them once, on the host side). */
+struct whmr_adam_guard_cfg { double max_norm; int32_t skip_nonfinite; int32_t pad; };
+struct whmr_adam_guard_state { float grad_norm, clip_coef; int32_t apply; int32_t pad; long long steps_seen, steps_skipped; };
+/* partials[b] = sum of g^2 over the 4096-element chunk workgroup b owns (grid and item lookup of whmr_adam_step; every one of the total_blocks
+ * doubles is written, no memset needed): the reduction torch.nn.utils.clip_grad_norm_ (get_total_norm: one norm launch per tensor + a stack + a
+ * norm) makes over p.grad of all parameters.  The reference does not clip (core/trainer.py:112-117 is a bare Adam): off by default. */
+int whmr_adam_grad_sumsq(const void* items, int n_items, int total_blocks, void* partials, void* stream);
+/* one workgroup: sums partials in a fixed order, writes state from cfg (clip_grad_norm_'s clip_coef_clamped = clamp(max_norm / (total_norm + 1e-6),
+ * max=1); the `if not torch.isfinite(total_norm)` a training loop would need a host read for), and -- unless the step is skipped -- does
+ * whmr_adam_advance's work (torch: _get_value(step) += 1 and the bias corrections of torch.optim.Adam's step()) */
+int whmr_adam_guard_advance(void* items, int n_items, const void* hyper, const void* partials, int total_blocks, const void* cfg, void* state,
+                            void* stream);
+/* whmr_adam_step with g replaced by fp32(g * state->clip_coef) -- clip_grad_norm_'s in-place p.grad.mul_(clip_coef) followed by
+ * self.optimizer.step() (core/trainer.py:615), without rewriting p.grad -- and nothing done at all when state->apply == 0 */
+int whmr_adam_step_guarded(const void* items, int n_items, int total_blocks, const void* hyper, const void* state, void* stream);
 /* LayerNorm backward: dx = dLN(x; gamma)(dy) + dres (dres nullable, dx may alias it); dgamma/dbeta (+)=; scratch >= 2048*C floats.
  * cast_out (nullable) [rows, C] bf16 = dx * row_scale[row] (row_scale nullable): the operand of the next branch's backward GEMMs, stochastic-depth
  * factor included (vit.py:132-139), written by the same pass. */

@@ -119,6 +119,17 @@ class _WhmrAdamItem(C.Structure):
                 + [('bc1', C.c_double), ('bc2', C.c_double)])
 
 
+class _WhmrAdamGuardCfg(C.Structure):
+    """struct whmr_adam_guard_cfg (include/whmr_hip.h): the host-pushed row of the gradient guard; max_norm <= 0: no clipping"""
+    _fields_ = [('max_norm', C.c_double), ('skip_nonfinite', C.c_int32), ('pad', C.c_int32)]
+
+
+class _WhmrAdamGuardState(C.Structure):
+    """struct whmr_adam_guard_state (include/whmr_hip.h): what whmr_adam_guard_advance writes and whmr_adam_step_guarded reads"""
+    _fields_ = [('grad_norm', C.c_float), ('clip_coef', C.c_float), ('apply', C.c_int32), ('pad', C.c_int32), ('steps_seen', C.c_longlong),
+                ('steps_skipped', C.c_longlong)]
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_long
 _SIGS = {
     'whmr_gemm_bf16': [C.POINTER(WhmrGemm), _I, _P],
@@ -230,6 +241,9 @@ _SIGS = {
     'whmr_weights_prepare': [_P, _I, _I, _P],
     'whmr_adam_advance': [_P, _I, _P, _P],
     'whmr_adam_step': [_P, _I, _I, _P, _P],
+    'whmr_adam_grad_sumsq': [_P, _I, _I, _P, _P],
+    'whmr_adam_guard_advance': [_P, _I, _P, _P, _I, _P, _P, _P],
+    'whmr_adam_step_guarded': [_P, _I, _I, _P, _P, _P],
     'whmr_augment_crop': [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     'whmr_augment_labels': [_P, _I, C.POINTER(_WhmrAugmentLabelsIO), _P],
     'whmr_maxpool_nhwc': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -1520,6 +1534,35 @@ def adam_step(items, n_items, total_blocks, hyper):
     _dev(items, hyper)
     assert items.dtype == torch.uint8 and items.numel() >= n_items * C.sizeof(_WhmrAdamItem) and hyper.dtype == torch.uint8
     _check(lib().whmr_adam_step(items.data_ptr(), n_items, total_blocks, hyper.data_ptr(), _stream()), 'whmr_adam_step')
+
+
+def _adam_guard_args(items, n_items, total_blocks, hyper, partials=None, cfg=None, state=None):
+    _dev(items, hyper, partials, cfg, state)
+    assert items.dtype == torch.uint8 and items.numel() >= n_items * C.sizeof(_WhmrAdamItem) and (hyper is None or hyper.dtype == torch.uint8)
+    assert partials is None or (partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= total_blocks)
+    assert cfg is None or cfg.numel() * cfg.element_size() >= C.sizeof(_WhmrAdamGuardCfg)
+    assert state is None or state.numel() * state.element_size() >= C.sizeof(_WhmrAdamGuardState)
+
+
+def adam_grad_sumsq(items, n_items, total_blocks, partials):
+    """partials (float64 device tensor, >= total_blocks): sum of g^2 per workgroup of the step's grid, every entry written (csrc/adam.hip)"""
+    _adam_guard_args(items, n_items, total_blocks, None, partials)
+    _check(lib().whmr_adam_grad_sumsq(items.data_ptr(), n_items, total_blocks, partials.data_ptr(), _stream()), 'whmr_adam_grad_sumsq')
+
+
+def adam_guard_advance(items, n_items, hyper, partials, total_blocks, cfg, state):
+    """cfg / state: device buffers holding struct whmr_adam_guard_cfg / whmr_adam_guard_state.  Norm, clip coefficient, decision and counters into
+    state; adam_advance's work unless the step is skipped"""
+    _adam_guard_args(items, n_items, total_blocks, hyper, partials, cfg, state)
+    _check(lib().whmr_adam_guard_advance(items.data_ptr(), n_items, hyper.data_ptr(), partials.data_ptr(), total_blocks, cfg.data_ptr(),
+                                         state.data_ptr(), _stream()), 'whmr_adam_guard_advance')
+
+
+def adam_step_guarded(items, n_items, total_blocks, hyper, state):
+    """adam_step on fp32(g * state.clip_coef); nothing at all when state.apply == 0"""
+    _adam_guard_args(items, n_items, total_blocks, hyper, state=state)
+    _check(lib().whmr_adam_step_guarded(items.data_ptr(), n_items, total_blocks, hyper.data_ptr(), state.data_ptr(), _stream()),
+           'whmr_adam_step_guarded')
 
 
 def layernorm_bwd(x, dy, gamma, dres, dx, dgamma, dbeta, eps, accumulate=False, cast_out=None, row_scale=None):

@@ -14,11 +14,27 @@ What lives where:
   copy from a pinned staging buffer that is never rewritten (a copy recorded during a capture replays from that host memory).
 * ``step()`` never synchronises and never reads device memory on the host.
 
+The gradient guard (off by default; the reference does not clip, trainer.py:112-117 is a bare Adam): ``max_grad_norm`` and ``skip_nonfinite`` are
+attributes of the optimizer -- NOT keys of ``param_groups`` / ``defaults``, so ``state_dict()`` stays torch's -- pushed to the device like ``lr``.  A
+guarded step is three launches (whmr_adam_grad_sumsq, whmr_adam_guard_advance, whmr_adam_step_guarded): the global L2 norm of the gradients the
+table points at, then ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` + Adam, with two differences by design:
+
+* ``p.grad`` is NOT rewritten: the update multiplies each gradient element by the coefficient on its way in (rounded to fp32 once, the value torch's
+  in-place ``mul_`` would have left); writing it back would be 4 B per parameter of traffic for nothing.  Read ``clip_coef`` if you need it.
+* with ``skip_nonfinite`` a step whose norm is NaN / Inf changes nothing on the device -- no p, exp_avg, exp_avg_sq, step count, bias correction or
+  bf16 operand copy -- and the next good step is Adam step t + 1 of the steps APPLIED.  The host cannot know (it never reads), so its bookkeeping
+  (``mark_updated()``: version bumps) runs regardless: a skipped step costs the version-keyed weight caches one spurious rebuild.
+
+``grad_norm`` / ``clip_coef`` / ``steps_skipped`` / ``steps_seen`` are views into one persistent device buffer that every guarded step, eager or
+replayed, writes: a loop may ``torch.stack`` them into a log without synchronising; ``guard_summary()`` is the one host read.  The counters are not
+part of ``state_dict()``.
+
 The library's weight caches are keyed on ``Parameter._version`` (models/*: ``_wcache``, L.WeightOperands); torch's in-place update bumps it, a
 raw kernel does not, so ``step()`` calls ``torch.autograd.graph.increment_version`` on every parameter it updated (and ``mark_updated()`` does the
 same after a graph replay, where no Python of ``step()`` runs).
 """
 import ctypes
+import math
 import struct
 
 import torch
@@ -29,13 +45,21 @@ _ITEM = struct.Struct('<7Qq6i2d')              # struct whmr_adam_item (include/
 assert _ITEM.size == ctypes.sizeof(L._WhmrAdamItem)
 _HYPER = struct.Struct('<3d2f')                 # struct whmr_adam_hyper: betas and lr as doubles (1 - beta, 1 - beta^t and lr / bc1 are formed in double on the device)
 assert _HYPER.size == ctypes.sizeof(L._WhmrAdamHyper)
+_GUARD_CFG = struct.Struct('<d2i')              # struct whmr_adam_guard_cfg: max_norm (<= 0: no clipping), skip_nonfinite, pad
+assert _GUARD_CFG.size == ctypes.sizeof(L._WhmrAdamGuardCfg)
+_GUARD_STATE = struct.Struct('<2f2i2q')         # struct whmr_adam_guard_state: grad_norm, clip_coef, apply, pad, steps_seen, steps_skipped
+assert _GUARD_STATE.size == ctypes.sizeof(L._WhmrAdamGuardState)
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False, differentiable=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False, differentiable=False,
+                 max_grad_norm=None, skip_nonfinite=False):
         for name, value in (('amsgrad', amsgrad), ('maximize', maximize), ('differentiable', differentiable)):
             if value:
                 raise ValueError('FusedAdam implements plain Adam only: %s is not supported' % name)
+        self._max_grad_norm, self._skip_nonfinite = self._check_guard(max_grad_norm, skip_nonfinite)
+        self._guard_cfg = self._guard_cfg_staging = self._guard_pushed = None
+        self._guard_state = self._partials = None
         # every key torch.optim.Adam keeps in a group, so that a state_dict() of either loads into the other
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None, capturable=True,
                         differentiable=False, fused=None, decoupled_weight_decay=False)
@@ -62,6 +86,16 @@ class FusedAdam(torch.optim.Optimizer):
         b1, b2 = group['betas']
         if group['lr'] < 0.0 or group['eps'] < 0.0 or group['weight_decay'] < 0.0 or not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError('invalid Adam hyper-parameters: %r' % {k: group[k] for k in ('lr', 'betas', 'eps', 'weight_decay')})
+
+    @staticmethod
+    def _check_guard(max_grad_norm, skip_nonfinite):
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, (torch.Tensor, bool)) or not isinstance(max_grad_norm, (int, float)):
+                raise ValueError('FusedAdam: max_grad_norm is None or a Python float (got %r)' % (max_grad_norm,))
+            max_grad_norm = float(max_grad_norm)
+            if not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
+                raise ValueError('FusedAdam: max_grad_norm must be None or a finite float > 0 (got %r); the norm is the L2 norm' % max_grad_norm)
+        return max_grad_norm, bool(skip_nonfinite)
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -132,13 +166,100 @@ class FusedAdam(torch.optim.Optimizer):
             opt.attach_operands(vit.__dict__['_train_operands'])
         return opt
 
+    # ------------------------------------------------------------------ gradient guard
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @property
+    def skip_nonfinite(self):
+        return self._skip_nonfinite
+
+    @property
+    def guarded(self):
+        return self._max_grad_norm is not None or self._skip_nonfinite
+
+    _KEEP = object()
+
+    def set_grad_guard(self, max_grad_norm=_KEEP, skip_nonfinite=_KEEP):
+        """Change the guard (an argument left out keeps its value; ``max_grad_norm=None`` stops clipping).  The device row follows at the next eager
+        ``step()`` or ``sync_hyperparameters()`` -- between two replays of a captured guarded step that is the caller's line.  A step captured
+        UNGUARDED stays unguarded: the guard's launches are not in that graph."""
+        self._max_grad_norm, self._skip_nonfinite = self._check_guard(self._max_grad_norm if max_grad_norm is self._KEEP else max_grad_norm,
+                                                                      self._skip_nonfinite if skip_nonfinite is self._KEEP else skip_nonfinite)
+
+    def _guard_view(self, dtype, index):
+        if self._guard_state is None:
+            raise RuntimeError('FusedAdam: no guarded step has run yet (max_grad_norm / skip_nonfinite are off, or step() was not called)')
+        return self._guard_state.view(dtype)[index]
+
+    @property
+    def grad_norm(self):
+        """0-dim fp32 device tensor: global L2 norm of the gradients the last executed guarded step saw, before clipping.  No synchronisation."""
+        return self._guard_view(torch.float32, 0)
+
+    @property
+    def clip_coef(self):
+        """0-dim fp32 device tensor: the factor the last executed guarded step applied to every gradient (1.0 when it did not clip, 0.0 when it
+        was skipped)"""
+        return self._guard_view(torch.float32, 1)
+
+    @property
+    def steps_seen(self):
+        """0-dim int64 device tensor: guarded steps executed so far, skipped ones included"""
+        return self._guard_view(torch.int64, 2)
+
+    @property
+    def steps_skipped(self):
+        """0-dim int64 device tensor: guarded steps that changed nothing because the norm was not finite"""
+        return self._guard_view(torch.int64, 3)
+
+    def guard_summary(self):
+        """The guard's state as Python numbers.  This is the one host read: it synchronises with the device."""
+        if self._guard_state is None:
+            return dict(grad_norm=None, clip_coef=None, applied=None, steps_seen=0, steps_skipped=0)
+        norm, coef, apply, _, seen, skipped = _GUARD_STATE.unpack(self._guard_state.cpu().numpy().tobytes())
+        return dict(grad_norm=norm, clip_coef=coef, applied=bool(apply), steps_seen=seen, steps_skipped=skipped)
+
+    def _guard_buffers(self, capturing):
+        """the state buffer and the partial sums (one double per workgroup, sized like ``_table`` for every parameter rather than for this upload):
+        created by the first eager guarded step, never inside a capture"""
+        need = self._partials_capacity()
+        if self._guard_state is not None and self._partials is not None and self._partials.numel() >= need:
+            return
+        if capturing:
+            raise RuntimeError('FusedAdam: the gradient guard\'s device buffers would be created inside a graph capture (their fill would be replayed, '
+                               'and a replay must write the buffer you read); run a warm-up step with the guard on first')
+        if self._guard_state is None:
+            self._guard_state = torch.zeros(_GUARD_STATE.size // 8, dtype=torch.int64, device=self._device)
+            self._guard_state.view(torch.float32)[1] = 1.0
+        if self._partials is None or self._partials.numel() < need:
+            self._partials = torch.empty(need, dtype=torch.float64, device=self._device)
+
+    def _partials_capacity(self):
+        """workgroups of a table holding EVERY parameter (one double each): a step over fewer gradients, or after the operands were detached
+        (tiles of a matrix are never fewer than its chunks), fits the same buffer"""
+        copies = self._wo.copies if self._wo is not None else {}
+        total = 0
+        for group in self.param_groups:
+            for p in group['params']:
+                ent = copies.get(id(p))
+                if ent is not None:
+                    N, K = ent[0].shape
+                    total += ((N + 63) // 64) * ((K + 63) // 64)
+                else:
+                    total += (p.numel() + L.ADAM_CHUNK - 1) // L.ADAM_CHUNK
+        return max(1, total)
+
     # ------------------------------------------------------------------ device rows
     def _rows(self):
         return [(float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay'])) for g in self.param_groups]
 
     def sync_hyperparameters(self):
-        """Push lr / betas / eps / weight_decay of every group to the device rows if they changed (on the current stream, no synchronisation).
-        An eager step() does this itself; between two replays of a captured step it is the caller's line after changing ``param_groups``."""
+        """Push lr / betas / eps / weight_decay of every group -- and the gradient guard's row -- to the device if they changed (on the current
+        stream, no synchronisation).  An eager step() does this itself; between two replays of a captured step it is the caller's line after
+        changing ``param_groups`` or calling ``set_grad_guard``."""
+        self._sync_guard()
         rows = self._rows()
         if rows == self._hyper_pushed:
             return
@@ -158,6 +279,21 @@ class FusedAdam(torch.optim.Optimizer):
                                                                                                          # reads the previous one
             self._hyper.copy_(self._hyper_staging, non_blocking=True)
         self._hyper_pushed = rows
+
+    def _sync_guard(self):
+        """the guard's row, pushed as the hyper-parameter rows are.  Nothing exists, and nothing is pushed, until the guard is first switched on."""
+        row = (self._max_grad_norm if self._max_grad_norm is not None else 0.0, int(self._skip_nonfinite))
+        if row == self._guard_pushed or (self._guard_cfg is None and not self.guarded):
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedAdam: the gradient guard changed inside a graph capture; the recorded copy would reset it at every replay -- '
+                               'run a warm-up step (or sync_hyperparameters()) before the capture')
+        with torch.cuda.device(self._device):
+            if self._guard_cfg is None:
+                self._guard_cfg = torch.zeros(_GUARD_CFG.size, dtype=torch.uint8, device=self._device)
+            self._guard_cfg_staging = torch.frombuffer(bytearray(_GUARD_CFG.pack(row[0], row[1], 0)), dtype=torch.uint8).pin_memory()   # fresh per push
+            self._guard_cfg.copy_(self._guard_cfg_staging, non_blocking=True)
+        self._guard_pushed = row
 
     def _capacity(self):
         return max(1, sum(len(g['params']) for g in self.param_groups)) * _ITEM.size
@@ -249,11 +385,17 @@ class FusedAdam(torch.optim.Optimizer):
             return loss
         self.sync_hyperparameters()
         with torch.cuda.device(self._device):
+            if self.guarded:
+                self._guard_buffers(capturing)
             # a captured step always records its own upload: the replay then does not depend on what eager steps wrote into the table since
             if capturing or key != self._key:
                 self._upload(live, capturing)
                 self._key = None if capturing else key       # a recorded upload has not run: the table still holds the last eager one
-            if self._n_items:
+            if self._n_items and self.guarded:
+                L.adam_grad_sumsq(self._table, self._n_items, self._blocks, self._partials)
+                L.adam_guard_advance(self._table, self._n_items, self._hyper, self._partials, self._blocks, self._guard_cfg, self._guard_state)
+                L.adam_step_guarded(self._table, self._n_items, self._blocks, self._hyper, self._guard_state)
+            elif self._n_items:
                 L.adam_advance(self._table, self._n_items, self._hyper)
                 L.adam_step(self._table, self._n_items, self._blocks, self._hyper)
         self._updated = [p for p, _, _, _ in live]
