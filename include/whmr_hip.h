@@ -350,6 +350,26 @@ int whmr_crop_normalize(const uint8_t* frame, int H, int W, long row_stride, con
                         int patch_h, int x_begin, int x_end, float* out, uint8_t* raw, const float* mean3, const float* std3,
                         void* stream);
 
+/* ---- clip inference, input side (csrc/frames.hip): the two preparations above the model call of demo/tester.py:95-146 for MANY frames.
+ * whmr_crop_normalize_frames: whmr_crop_normalize over a DEVICE table of P whmr_frame_crop_item, one per detection -- its frame (uint8 HWC,
+ * row_stride bytes per row; frames may differ in size and stride) and its inverse 2x3 map -- so all persons of all frames leave in one launch.
+ * Same arithmetic (shared device code), same outputs: out [P, 3, patch_h, x_end - x_begin] fp32; raw (nullable) [P, patch_h, x_end - x_begin, 3]. */
+struct whmr_frame_crop_item {
+    const uint8_t* frame; int32_t H, W; int64_t row_stride; double inv[6];
+};
+int whmr_crop_normalize_frames(const void* items, int P, int patch_w, int patch_h, int x_begin, int x_end, float* out, uint8_t* raw,
+                               const float* mean3, const float* std3, void* stream);
+/* Normalize(ToTensor(Resize)) of F uint8 frames [F, H, W, 3] of one size (tester.py:47-53,101-103) -> out [F, 3, h, w] fp32 and (nullable) out_u8
+ * [F, h, w, 3], the resized bytes.  The resize is Pillow's Image.resize((w, h), BILINEAR) bit for bit: triangle filter of support max(1, in / out),
+ * float64 taps normalised and rounded to 22 fractional bits, 8-bit horizontal pass into `mid`, then the vertical pass; an axis whose size does not
+ * change is copied.  out = (v / 255 - mean) / std with two true fp32 divisions.  whmr_resize_coeffs builds the tap tables of (W -> w, H -> h) on the
+ * device into coef: w rows of 2 + kx int32 (first tap, count, taps), then h rows of 2 + ky, k = 2 ceil(max(1, in / out)) + 1 -- build once per size,
+ * keep.  mid: caller-owned scratch of F * H rows of pitch = 16 ceil(12 ceil(w / 4) / 16) bytes, 16-byte aligned.  coef_words / mid_bytes: the
+ * capacities, checked.  Two launches (one for the tables), no allocation, no synchronisation, bit-reproducible. */
+int whmr_resize_coeffs(int in_w, int out_w, int in_h, int out_h, int32_t* coef, long coef_words, void* stream);
+int whmr_resize_normalize_frames(const uint8_t* frames, int F, int H, int W, int h, int w, const int32_t* coef, long coef_words, uint8_t* mid,
+                                 long mid_bytes, float* out, uint8_t* out_u8, const float* mean3, const float* std3, void* stream);
+
 /* ---- backward-pass helpers of the ViT backbone (autograd of vit.py:61-140,313-332; driven by core/trainer.py:410-470).
  * The backward matrix products run on whmr_gemm_bf16 / whmr_gemm_f32: dX = dY.W uses W^T as the weight operand,
  * dW = dY^T.X uses the transposed activations -- both produced by whmr_transpose_cast. */

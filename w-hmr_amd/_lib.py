@@ -80,6 +80,14 @@ class _WhmrAugmentLabelsIO(C.Structure):
 AUGMENT_ITEM_FORMAT = '<Q5q12i26d'          # struct whmr_augment_item (include/whmr_hip.h), 304 bytes
 
 
+FRAME_CROP_ITEM_FORMAT = '<Q2iq6d'          # struct whmr_frame_crop_item (include/whmr_hip.h), 72 bytes
+
+
+class _WhmrFrameCropItem(C.Structure):
+    """struct whmr_frame_crop_item (include/whmr_hip.h): one detection of whmr_crop_normalize_frames (rows are packed with FRAME_CROP_ITEM_FORMAT)"""
+    _fields_ = [('frame', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('row_stride', C.c_int64), ('inv', C.c_double * 6)]
+
+
 class WhmrTnItem(C.Structure):
     """struct whmr_tn_item (include/whmr_hip.h): one product of a grouped weight-gradient launch"""
     _fields_ = [('A', C.c_void_p), ('lda', C.c_long), ('B', C.c_void_p), ('ldb', C.c_long), ('C', C.c_void_p), ('ldc', C.c_long),
@@ -186,6 +194,9 @@ _SIGS = {
     'whmr_smpl_joints': [C.POINTER(WhmrSmplModel), _P, _P, _I, _P, _P, _P, _P, _P],
     'whmr_maf_sample': [_P, _I, _L, _L, _L, _L, _I, _I, _P, _P, _P, _L, _F, _F, _F, C.POINTER(WhmrMafWeights), _I, _I, _P, _L, _P, _P],
     'whmr_crop_normalize': [_P, _I, _I, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    'whmr_crop_normalize_frames': [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    'whmr_resize_coeffs': [_I, _I, _I, _I, _P, _L, _P],
+    'whmr_resize_normalize_frames': [_P, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P],
     'whmr_attention_fwd_train': [_P, _P, _P, _I, _I, _I, _I, _F, _P],
     'whmr_attention_bwd': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     'whmr_tz_conv1': [_P, _I, _P, _P, _I, _I, _I, _P],
@@ -1393,6 +1404,69 @@ def crop_normalize(frame, inv_affine, patch_w, patch_h, x0, x1, out, raw, mean, 
     m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     _check(lib().whmr_crop_normalize(frame.data_ptr(), H, W, frame.stride(0), inv_affine.data_ptr(), inv_affine.shape[0], patch_w, patch_h,
                                      x0, x1, out.data_ptr(), _ptr(raw), m3, s3, _stream()), 'whmr_crop_normalize')
+    return out
+
+
+def crop_normalize_frames(items, P, patch_w, patch_h, x0, x1, out, raw, mean, std):
+    """whmr_crop_normalize over many frames (include/whmr_hip.h: whmr_crop_normalize_frames); items: the uploaded table of P whmr_frame_crop_item"""
+    _dev(items, out, raw)
+    assert items.dtype == torch.uint8 and items.is_contiguous() and items.numel() >= P * C.sizeof(_WhmrFrameCropItem)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (P, 3, patch_h, x1 - x0)
+    assert raw is None or (raw.dtype == torch.uint8 and raw.is_contiguous() and raw.shape == (P, patch_h, x1 - x0, 3))
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    _check(lib().whmr_crop_normalize_frames(items.data_ptr(), P, patch_w, patch_h, x0, x1, out.data_ptr(), _ptr(raw), m3, s3, _stream()),
+           'whmr_crop_normalize_frames')
+    return out
+
+
+def resize_ksize(in_size, out_size):
+    """taps per output pixel of Pillow's bilinear resize along one axis: 2 ceil(max(1, in / out)) + 1 (csrc/frames.hip computes the same)"""
+    return int(math.ceil(max(1.0, float(in_size) / float(out_size)))) * 2 + 1
+
+
+def resize_coef_words(H, W, h, w):
+    return w * (2 + resize_ksize(W, w)) + h * (2 + resize_ksize(H, h))
+
+
+def resize_mid_pitch(w):
+    """bytes per row of the horizontal pass's intermediate: 12 per group of four pixels, rounded up to 16"""
+    return ((w + 3) // 4 * 12 + 15) // 16 * 16
+
+
+_resize_coefs = {}
+
+
+def resize_coeffs(H, W, h, w, device):
+    """the device tap tables of (W -> w, H -> h), built by one small launch the first time a size is seen and kept (whmr_resize_coeffs)"""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError('whmr_amd kernels need a HIP device (got %s); there is no CPU fallback' % device)
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (device, H, W, h, w)
+    coef = _resize_coefs.get(key)
+    if coef is None:
+        coef = torch.empty(resize_coef_words(H, W, h, w), dtype=torch.int32, device=device)
+        _check(lib().whmr_resize_coeffs(W, w, H, h, coef.data_ptr(), coef.numel(), _stream()), 'whmr_resize_coeffs')
+        if torch.cuda.is_current_stream_capturing():                # a table built inside a capture exists only after a replay: not kept
+            return coef
+        torch.cuda.current_stream(device).synchronize()             # once per size: later calls may read the table from any stream
+        _resize_coefs[key] = coef
+    return coef
+
+
+def resize_normalize_frames(frames, h, w, coef, mid, out, out_u8, mean, std):
+    """frames uint8 [F, H, W, 3] -> out fp32 [F, 3, h, w] = Normalize(ToTensor(Pillow bilinear resize)), out_u8 (or None) [F, h, w, 3];
+    coef: resize_coeffs(H, W, h, w); mid: uint8 scratch of at least F * H * resize_mid_pitch(w) bytes (whmr_resize_normalize_frames)"""
+    _dev(frames, coef, mid, out, out_u8)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous()
+    F_, H, W = frames.shape[:3]
+    assert coef.dtype == torch.int32 and coef.is_contiguous() and mid.dtype == torch.uint8 and mid.is_contiguous()
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (F_, 3, h, w)
+    assert out_u8 is None or (out_u8.dtype == torch.uint8 and out_u8.is_contiguous() and out_u8.shape == (F_, h, w, 3))
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    _check(lib().whmr_resize_normalize_frames(frames.data_ptr(), F_, H, W, h, w, coef.data_ptr(), coef.numel(), mid.data_ptr(), mid.numel(),
+                                              out.data_ptr(), _ptr(out_u8), m3, s3, _stream()), 'whmr_resize_normalize_frames')
     return out
 
 

@@ -6,6 +6,8 @@ normalised patches for a whole frame: the uint8 frame is uploaded / read once, t
 built on the host exactly like gen_trans_from_patch_cv + cv2.getAffineTransform, the warp + ToTensor + Normalize run in
 ``whmr_crop_normalize``.  With ``x_slice=(32, 224)`` only the 192 columns the model consumes are computed.
 """
+import struct
+
 import numpy as np
 import torch
 
@@ -65,6 +67,57 @@ def crop_persons(frame, bboxes, crop_size=256, scale=1.0, x_slice=None, want_raw
     raw = torch.empty(B, crop_size, x1 - x0, 3, dtype=torch.uint8, device=frame.device) if want_raw else None
     L.crop_normalize(frame, inv_d, crop_size, crop_size, x0, x1, out, raw, MEAN, STD)
     return (out, raw) if want_raw else out
+
+
+def frame_index_of(dets_per_frame):
+    """int64 [P]: the frame of every detection of a clip, detections in frame order, then detection order (frames without detections: no entry)"""
+    counts = [len(d) for d in dets_per_frame]
+    return np.repeat(np.arange(len(counts), dtype=np.int64), counts)
+
+
+def _clip_frames(frames):
+    """list of uint8 [H_i, W_i, 3] device tensors / numpy arrays (uploaded once each), or one [F, H, W, 3] tensor -> list of device tensors"""
+    if torch.is_tensor(frames) or isinstance(frames, np.ndarray):
+        assert frames.ndim == 4, 'one tensor of frames is [F, H, W, 3]'
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
+        return list(frames.unbind(0))
+    return [torch.from_numpy(np.ascontiguousarray(f)).cuda() if isinstance(f, np.ndarray) else f for f in frames]
+
+
+@torch.no_grad()
+def crop_persons_frames(frames, dets_per_frame, crop_size=256, scale=1.0, x_slice=None, want_raw=False):
+    """``crop_persons`` for a clip in ONE launch.  frames: list of uint8 [H_i, W_i, 3] RGB frames (device tensors, rows may be strided; numpy arrays are
+    uploaded once each; sizes may differ) or one [F, H, W, 3] tensor; dets_per_frame: per frame its list of (c_x, c_y, w, h), possibly empty.
+    Returns (patches [P, 3, crop_size, x1 - x0] fp32, frame_index int64 [P] on the device) -- (patches, raw uint8 [P, crop_size, x1 - x0, 3],
+    frame_index) with want_raw; detections in frame order, then detection order.  Each patch equals ``crop_persons`` of its frame bit for bit."""
+    frames = _clip_frames(frames)
+    if len(frames) != len(dets_per_frame):
+        raise ValueError('%d frames but detections for %d' % (len(frames), len(dets_per_frame)))
+    index = frame_index_of(dets_per_frame)
+    P = len(index)
+    x0, x1 = x_slice if x_slice is not None else (0, crop_size)
+    rows = []
+    for f, (frame, dets) in enumerate(zip(frames, dets_per_frame)):
+        if not len(dets):
+            continue
+        if not frame.is_cuda:
+            raise RuntimeError('crop_persons_frames runs on a HIP device only (no CPU fallback)')
+        assert frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.stride(2) == 1 and frame.stride(1) == 3
+        for b in dets:
+            inv = _invert_affine(gen_trans_from_patch_cv(b[0], b[1], b[2], b[3], crop_size, crop_size, scale, 0))
+            rows.append(struct.pack(L.FRAME_CROP_ITEM_FORMAT, frame.data_ptr(), frame.shape[0], frame.shape[1], frame.stride(0), *inv))
+    dev = next((f.device for f in frames if torch.is_tensor(f) and f.is_cuda), None)
+    if dev is None:
+        raise RuntimeError('crop_persons_frames runs on a HIP device only (no CPU fallback)')
+    out = torch.empty(P, 3, crop_size, x1 - x0, dtype=torch.float32, device=dev)
+    raw = torch.empty(P, crop_size, x1 - x0, 3, dtype=torch.uint8, device=dev) if want_raw else None
+    index_d = torch.from_numpy(index).pin_memory().to(dev, non_blocking=True)
+    if P:
+        staging = torch.frombuffer(bytearray(b''.join(rows)), dtype=torch.uint8).pin_memory()       # a fresh pinned buffer per call: the copy is in flight
+        table = staging.to(dev, non_blocking=True)                                                     # the one upload of the table
+        L.crop_normalize_frames(table, P, crop_size, crop_size, x0, x1, out, raw, MEAN, STD)
+    return (out, raw, index_d) if want_raw else (out, index_d)
 
 
 def get_single_image_crop_demo(image, bbox, kp_2d=None, scale=1.2, crop_size=224):

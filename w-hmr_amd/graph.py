@@ -4,6 +4,9 @@ launch cost dominates; a captured graph replays them with one submission).
     fast = GraphedForward(model, x, None, center, scale, bbox_height, orig_shape, bbox_info, full_x=full)
     out = fast(x2, None, center2, ...)        # same shapes; inputs are copied into the captured buffers
 
+Every tensor argument, positional or keyword, is a static input: it is cloned at capture and refreshed by ``copy_`` before each replay -- the
+int64 ``frame_index`` of clip inference (whmr_amd.demo.ClipPipeline) like the float inputs.
+
 Every kernel of libwhmr_hip.so only enqueues on the stream it is given and allocates nothing, so capture needs no
 special casing; tensor allocations made by the module during capture live in the graph's private pool.
 """

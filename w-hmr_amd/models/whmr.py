@@ -612,8 +612,9 @@ class WHMR(nn.Module):
         return st if st is not None else L.side_stream(dev, 0 if tag == 'tz' else 1)      # the package's shared pool (module-level, not in the module: deepcopy / pickling)
 
     @torch.no_grad()
-    def _camera(self, full_x, cam_rotmat, B, dev):
-        """whmr.py:509-524: camera-calibration head on the full image -> (cam_rotmat, render_rotmat); detached in the reference too."""
+    def _camera(self, full_x, cam_rotmat, B, dev, frame_index=None):
+        """whmr.py:509-524: camera-calibration head on the full image -> (cam_rotmat, render_rotmat); detached in the reference too.
+        frame_index [B] (clip inference): full_x holds F frames, the head runs at batch F and person b takes the rows of frame frame_index[b]."""
         render_rotmat = None
         if cam_rotmat is None:
             if full_x is not None:
@@ -631,6 +632,9 @@ class WHMR(nn.Module):
                                                                   for i, pr in enumerate(pred))):
                     logits = torch.cat([pr.float() for pr in pred], 1)
                 from .cam_model import PITCH_RANGE, ROLL_RANGE
+                if frame_index is not None:                                       # F frames -> [F, 3, 3], then a device gather per person (no host read)
+                    cam_f, ren_f = L.cam_head(logits, pred[0].shape[1], PITCH_RANGE, ROLL_RANGE, full_x.shape[0])
+                    return cam_f.index_select(0, frame_index), ren_f.index_select(0, frame_index)
                 cam_rotmat, render_rotmat = L.cam_head(logits, pred[0].shape[1], PITCH_RANGE, ROLL_RANGE, B)
             else:
                 cam_rotmat = torch.eye(3, device=dev).unsqueeze(0).expand(B, -1, -1).float()
@@ -640,17 +644,23 @@ class WHMR(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, meta_masks=None, center=None, scale=None, bbox_height=None, orig_shape=None, bbox_info=None,
-                is_train=False, J_regressor=None, full_x=None, cam_rotmat=None, view=None):
+                is_train=False, J_regressor=None, full_x=None, cam_rotmat=None, view=None, frame_index=None):
+        """frame_index (eval only, clip inference): int64 [B] on the device -- full_x then holds F frames and person b belongs to frame frame_index[b];
+        without it full_x has batch 1 (one frame, broadcast) or batch B (one per person)."""
         if not x.is_cuda:
             raise RuntimeError('whmr_amd.WHMR runs on a HIP device only (no CPU fallback)')
+        if frame_index is not None and is_train:
+            raise ValueError('frame_index belongs to the inference path (is_train=False)')
+        if not is_train and cam_rotmat is None:                              # (a given cam_rotmat takes the place of full_x)
+            check_full_x_batch(full_x, x.shape[0], frame_index)
         if is_train:       # training graph: HIP forward kernels + hand-written HIP backward behind autograd nodes (whmr_amd.train)
             from ..train.whmr_train import whmr_forward_train
             return whmr_forward_train(self, x, center, scale, bbox_height, orig_shape, bbox_info, J_regressor=J_regressor,
                                       full_x=full_x, cam_rotmat=cam_rotmat)
         with torch.no_grad():
-            return self._forward_eval(x, center, scale, bbox_height, orig_shape, bbox_info, J_regressor, full_x, cam_rotmat, view)
+            return self._forward_eval(x, center, scale, bbox_height, orig_shape, bbox_info, J_regressor, full_x, cam_rotmat, view, frame_index)
 
-    def _forward_eval(self, x, center, scale, bbox_height, orig_shape, bbox_info, J_regressor, full_x, cam_rotmat, view):
+    def _forward_eval(self, x, center, scale, bbox_height, orig_shape, bbox_info, J_regressor, full_x, cam_rotmat, view, frame_index=None):
         view = view or self.return_view
         with_aux = view == 'train'
         B, dev = x.shape[0], x.device
@@ -671,17 +681,17 @@ class WHMR(nn.Module):
             if self.camera_launch == 'early':
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    cam_rotmat, render_rotmat = self._camera(full_x, None, B, dev)
+                    cam_rotmat, render_rotmat = self._camera(full_x, None, B, dev, frame_index)
             else:
                 cam_pending = torch.cuda.Event()
                 cam_pending.record(main)
         else:
-            cam_rotmat, render_rotmat = self._camera(full_x, cam_rotmat, B, dev)
+            cam_rotmat, render_rotmat = self._camera(full_x, cam_rotmat, B, dev, frame_index)
 
         def launch_camera():
             side.wait_event(cam_pending)
             with torch.cuda.stream(side):
-                return self._camera(full_x, None, B, dev)
+                return self._camera(full_x, None, B, dev, frame_index)
 
         # backbone (tokens are NHWC already) -> deconv pyramid in NHWC
         vit = self.feature_extractor.backbone
@@ -784,6 +794,26 @@ class WHMR(nn.Module):
                 'pred_cam_t': smpl_output['pred_cam_t'], 'focal_length': smpl_output['focal_length'],
                 'cam_rotmat': cam_rotmat, 'render_rotmat': render_rotmat, 'shape': smpl_output['pred_shape'],
                 'global_pose': g_pose, 'local_pose': smpl_output['pose']}
+
+
+def check_full_x_batch(full_x, B, frame_index=None):
+    """The three accepted forms of the camera input of the inference path, by shape alone (raises ValueError before anything is launched):
+    batch 1 (one frame, its camera broadcast to all B persons), batch B (one image per person: demo/tester.py:161), or -- with frame_index [B] --
+    batch F (the frames of a clip, person b in frame frame_index[b]).  -> 'none' | 'broadcast' | 'per_person' | 'frames'."""
+    if full_x is None:
+        return 'none'
+    n = full_x.shape[0]
+    if frame_index is not None:
+        if frame_index.dim() != 1 or frame_index.shape[0] != B or frame_index.dtype != torch.int64:
+            raise ValueError('frame_index must be int64 [%d] (one frame per person), got %s %s' % (B, frame_index.dtype, tuple(frame_index.shape)))
+        if n < 1:
+            raise ValueError('full_x holds no frame')
+        return 'frames'
+    if n == 1:
+        return 'broadcast'
+    if n == B:
+        return 'per_person'
+    raise ValueError('full_x has batch %d: expected 1 (one frame for all persons), %d (one per person), or the frames of a clip with frame_index' % (n, B))
 
 
 THIRD_PARTY_KEY_PARTS = ('.smpl.', '.vertex_joint_selector.')     # smplx / pare internals inside regressor.N (SURVEY App. B); 'transformer.' = HF leftovers
