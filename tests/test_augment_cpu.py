@@ -1,16 +1,13 @@
 """Training-batch maker, host side: the numpy restatement (tests/augment_reference.py) against the fixture recorded from the imported reference
-(tests/golden/augment.npz, tests/golden/make_golden_augment.py), the package's random draws and host geometry, and the C struct layouts."""
-import ctypes
+(tests/golden/augment.npz, tests/golden/make_golden_augment.py), the package's random draws and host geometry."""
 import os
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import augment_reference as AR
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 
 EXACT = ('keypoints', 'smpl_2dkps', 'keypoints_world', 'betas', 'has_smpl', 'has_pose_3d', 'scale', 'center', 'orig_shape', 'is_flipped', 'rot_angle',
          'gender', 'sample_index', 'bbox_height', 'bbox_width', 'focal', 'bbox_info')
@@ -122,24 +119,6 @@ def test_flat_saturated_region_survives_rotation_and_resize():
     for dtype in (np.float64, np.float32):
         p = AR.rgb_patch(img, [60.0, 60.0], 0.2, 33.3, 0, [1.0, 1.0, 1.0], dtype)
         assert (p == 255).all()
-
-
-def test_table_structs_match_the_c_header_layout(tmp_path):
-    from whmr_amd import _lib as L
-    fields = ['img', 'row_stride', 'sample_index', 'rot_off', 'mid_off', 'coef_off', 'H', 'W', 'ul_x', 'ul_y', 'bw', 'bh', 'pad', 'flip', 'is_smpl',
-              'ksize_x', 'ksize_y', 'reserved', 'T', 'M', 'j3d_cs', 'aa_cs', 'pn', 'rot', 'scale', 'center']
-    sizes = [8] * 6 + [4] * 12 + [72, 48, 16, 16, 24, 8, 8, 16]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "whmr_hip.h"', 'int main(void) {',
-             '  printf("%zu\\n", sizeof(struct whmr_augment_item));', '  printf("%zu\\n", sizeof(struct whmr_augment_labels_io));']
-    lines += ['  printf("%%zu\\n", offsetof(struct whmr_augment_item, %s));' % f for f in fields]
-    lines += ['  printf("%%zu\\n", offsetof(struct whmr_augment_labels_io, %s));' % f for f, _ in L._WhmrAugmentLabelsIO._fields_]
-    lines += ['  return 0;', '}']
-    (tmp_path / 'l.c').write_text('\n'.join(lines))
-    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), str(tmp_path / 'l.c'), '-o', str(tmp_path / 'l')], check=True)
-    got = [int(v) for v in subprocess.run([str(tmp_path / 'l')], check=True, capture_output=True, text=True).stdout.split()]
-    assert got[0] == struct.calcsize(L.AUGMENT_ITEM_FORMAT) == 304 and got[1] == ctypes.sizeof(L._WhmrAugmentLabelsIO)
-    assert got[2:2 + len(fields)] == [int(v) for v in np.cumsum([0] + sizes[:-1])]               # '<' packs without padding: so must the C struct
-    assert got[2 + len(fields):] == [getattr(L._WhmrAugmentLabelsIO, f).offset for f, _ in L._WhmrAugmentLabelsIO._fields_]
 
 
 def test_maker_refuses_the_cpu(gold):

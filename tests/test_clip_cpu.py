@@ -1,17 +1,14 @@
 """Clip inference, the parts that need no GPU: the numpy restatement of Pillow's bilinear resize (tests/frames_reference.py) against the fixture
 recorded from Pillow (tests/golden/frames.npz) and against Pillow itself where it is installed; the host-side layout of a clip (frame_index order,
-padding, target size) and the ValueError paths, all of which are decided before any device call; the C layout of the crop table."""
-import ctypes
+padding, target size) and the ValueError paths, all of which are decided before any device call."""
 import os
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import frames_reference as FR
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 from whmr_amd import _lib as L
 from whmr_amd.datasets.img_utils import frame_index_of
 from whmr_amd.demo import clip_plan, padded_count, resize_target
@@ -107,23 +104,3 @@ def test_value_errors_come_before_any_device_call():
         check_full_x_batch(fx(2), 3, torch.tensor([0, 1]))                         # one frame index per person
     with pytest.raises(ValueError):
         check_full_x_batch(fx(2), 3, torch.tensor([0, 1, 1], dtype=torch.int32))
-
-
-def test_crop_table_row_matches_the_c_header(tmp_path):
-    """struct whmr_frame_crop_item: gcc's layout of include/whmr_hip.h == the ctypes mirror == the struct format the table is packed with"""
-    cls = L._WhmrFrameCropItem
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "whmr_hip.h"', 'int main(void) {',
-             '  printf("size %zu\\n", sizeof(struct whmr_frame_crop_item));']
-    for name, _ in cls._fields_:
-        lines.append('  printf("%s %%zu\\n", offsetof(struct whmr_frame_crop_item, %s));' % (name, name))
-    lines += ['  return 0;', '}']
-    src, exe = tmp_path / 'layout.c', tmp_path / 'layout'
-    src.write_text('\n'.join(lines))
-    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got['size']) == ctypes.sizeof(cls) == struct.calcsize(L.FRAME_CROP_ITEM_FORMAT) == 72
-    for name, _ in cls._fields_:
-        assert int(got[name]) == getattr(cls, name).offset, name
-    row = struct.pack(L.FRAME_CROP_ITEM_FORMAT, 0x1234, 7, 9, 27, *range(6))
-    it = cls.from_buffer_copy(row)
-    assert (it.frame, it.H, it.W, it.row_stride, list(it.inv)) == (0x1234, 7, 9, 27, [0.0, 1.0, 2.0, 3.0, 4.0, 5.0])

@@ -6,6 +6,7 @@ library is missing, or a tensor is not on a HIP device, these functions raise.
 import ctypes as C
 import math
 import os
+import struct
 
 import torch
 
@@ -77,15 +78,22 @@ class _WhmrAugmentLabelsIO(C.Structure):
         'o_has_pose_3d')]
 
 
-AUGMENT_ITEM_FORMAT = '<Q5q12i26d'          # struct whmr_augment_item (include/whmr_hip.h), 304 bytes
-
-
-FRAME_CROP_ITEM_FORMAT = '<Q2iq6d'          # struct whmr_frame_crop_item (include/whmr_hip.h), 72 bytes
+class _WhmrAugmentItem(C.Structure):
+    """struct whmr_augment_item (include/whmr_hip.h): one sample's geometry of whmr_augment_crop / whmr_augment_labels (rows are packed with AUGMENT_ITEM_FORMAT)"""
+    _fields_ = ([('img', C.c_void_p)] + [(k, C.c_int64) for k in ('row_stride', 'sample_index', 'rot_off', 'mid_off', 'coef_off')]
+                + [(k, C.c_int32) for k in ('H', 'W', 'ul_x', 'ul_y', 'bw', 'bh', 'pad', 'flip', 'is_smpl', 'ksize_x', 'ksize_y', 'reserved')]
+                + [('T', C.c_double * 9), ('M', C.c_double * 6), ('j3d_cs', C.c_double * 2), ('aa_cs', C.c_double * 2), ('pn', C.c_double * 3),
+                   ('rot', C.c_double), ('scale', C.c_double), ('center', C.c_double * 2)])
 
 
 class _WhmrFrameCropItem(C.Structure):
     """struct whmr_frame_crop_item (include/whmr_hip.h): one detection of whmr_crop_normalize_frames (rows are packed with FRAME_CROP_ITEM_FORMAT)"""
     _fields_ = [('frame', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('row_stride', C.c_int64), ('inv', C.c_double * 6)]
+
+
+class _WhmrWprepItem(C.Structure):
+    """struct whmr_wprep_item (include/whmr_hip.h): one weight matrix of whmr_weights_prepare (WeightOperands packs the rows)"""
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('dst_t', C.c_void_p)] + [(k, C.c_int32) for k in ('N', 'K', 'tile_begin', 'tiles_k')]
 
 
 class WhmrTnItem(C.Structure):
@@ -137,6 +145,34 @@ class _WhmrAdamGuardState(C.Structure):
     _fields_ = [('grad_norm', C.c_float), ('clip_coef', C.c_float), ('apply', C.c_int32), ('pad', C.c_int32), ('steps_seen', C.c_longlong),
                 ('steps_skipped', C.c_longlong)]
 
+
+# every struct of include/whmr_hip.h and its mirror: tests/test_abi_cpu.py compares names, sizes and field offsets with the header
+C_STRUCTS = {
+    'whmr_gemm': WhmrGemm, 'whmr_gemm_blk_desc': WhmrGemmBlk, 'whmr_gemm_blk_mx_desc': WhmrGemmBlkMx, 'whmr_tn_item': WhmrTnItem,
+    'whmr_smpl_model': WhmrSmplModel, 'whmr_maf_weights': WhmrMafWeights, 'whmr_stage_tail': WhmrStageTail,
+    'whmr_frame_crop_item': _WhmrFrameCropItem, 'whmr_wprep_item': _WhmrWprepItem,
+    'whmr_adam_hyper': _WhmrAdamHyper, 'whmr_adam_item': _WhmrAdamItem, 'whmr_adam_guard_cfg': _WhmrAdamGuardCfg, 'whmr_adam_guard_state': _WhmrAdamGuardState,
+    'whmr_loss_stage': _WhmrLossStage, 'whmr_loss_args': _WhmrLossArgs, 'whmr_augment_item': _WhmrAugmentItem, 'whmr_augment_labels_io': _WhmrAugmentLabelsIO,
+}
+_FORMAT_CODES = {C.c_void_p: 'Q', C.c_int32: 'i', C.c_int64: 'q', C.c_float: 'f', C.c_double: 'd'}
+
+
+def struct_format(cls):
+    """-> the little-endian ``struct`` format that packs a row of the mirror ``cls`` (scalar and array fields): one code per field, pointers as Q,
+    pad bytes wherever ctypes leaves a gap, so that its size is ctypes.sizeof(cls).  The tables uploaded to the device are packed with it."""
+    fmt, end = '<', 0
+    for name, t in cls._fields_:
+        n, t = (t._length_, t._type_) if issubclass(t, C.Array) else (1, t)
+        offset = getattr(cls, name).offset
+        fmt += '%dx' % (offset - end) if offset > end else ''
+        fmt += '%d%s' % (n, _FORMAT_CODES[t])
+        end = offset + n * C.sizeof(t)
+    return fmt + ('%dx' % (C.sizeof(cls) - end) if C.sizeof(cls) > end else '')
+
+
+AUGMENT_ITEM_FORMAT = struct_format(_WhmrAugmentItem)
+FRAME_CROP_ITEM_FORMAT = struct_format(_WhmrFrameCropItem)
+_WPREP_ITEM = struct.Struct(struct_format(_WhmrWprepItem))
 
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_long
 _SIGS = {
@@ -1560,7 +1596,6 @@ class WeightOperands:
     whenever a parameter's version moved -- the buffers (and so the pointers a captured graph holds) never change."""
 
     def __init__(self, params, shapes=None):
-        import struct
         self.params = list(params)
         dev = self.params[0].device
         shapes = shapes or {}
@@ -1572,7 +1607,7 @@ class WeightOperands:
             wt = torch.empty(K, N, dtype=torch.bfloat16, device=dev)
             self.copies[id(p)] = (w, wt)
             tk = (K + 63) // 64
-            rows.append(struct.pack('<QQQiiii', p.data_ptr(), w.data_ptr(), wt.data_ptr(), N, K, tb, tk))
+            rows.append(_WPREP_ITEM.pack(p.data_ptr(), w.data_ptr(), wt.data_ptr(), N, K, tb, tk))
             tb += ((N + 63) // 64) * tk
         self.total = tb
         self.table = torch.frombuffer(bytearray(b''.join(rows)), dtype=torch.uint8).to(dev)

@@ -33,7 +33,6 @@ The library's weight caches are keyed on ``Parameter._version`` (models/*: ``_wc
 raw kernel does not, so ``step()`` calls ``torch.autograd.graph.increment_version`` on every parameter it updated (and ``mark_updated()`` does the
 same after a graph replay, where no Python of ``step()`` runs).
 """
-import ctypes
 import math
 import struct
 
@@ -41,14 +40,11 @@ import torch
 
 from .. import _lib as L
 
-_ITEM = struct.Struct('<7Qq6i2d')              # struct whmr_adam_item (include/whmr_hip.h; ctypes mirror: _lib._WhmrAdamItem)
-assert _ITEM.size == ctypes.sizeof(L._WhmrAdamItem)
-_HYPER = struct.Struct('<3d2f')                 # struct whmr_adam_hyper: betas and lr as doubles (1 - beta, 1 - beta^t and lr / bc1 are formed in double on the device)
-assert _HYPER.size == ctypes.sizeof(L._WhmrAdamHyper)
-_GUARD_CFG = struct.Struct('<d2i')              # struct whmr_adam_guard_cfg: max_norm (<= 0: no clipping), skip_nonfinite, pad
-assert _GUARD_CFG.size == ctypes.sizeof(L._WhmrAdamGuardCfg)
-_GUARD_STATE = struct.Struct('<2f2i2q')         # struct whmr_adam_guard_state: grad_norm, clip_coef, apply, pad, steps_seen, steps_skipped
-assert _GUARD_STATE.size == ctypes.sizeof(L._WhmrAdamGuardState)
+# the packed rows of the device tables (include/whmr_hip.h; layouts: the ctypes mirrors of _lib)
+_ITEM = struct.Struct(L.struct_format(L._WhmrAdamItem))
+_HYPER = struct.Struct(L.struct_format(L._WhmrAdamHyper))                   # betas and lr as doubles (1 - beta, 1 - beta^t and lr / bc1 are formed in double on the device)
+_GUARD_CFG = struct.Struct(L.struct_format(L._WhmrAdamGuardCfg))           # max_norm (<= 0: no clipping), skip_nonfinite, pad
+_GUARD_STATE = struct.Struct(L.struct_format(L._WhmrAdamGuardState))       # grad_norm, clip_coef, apply, pad, steps_seen, steps_skipped
 
 
 class FusedAdam(torch.optim.Optimizer):
