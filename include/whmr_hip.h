@@ -370,6 +370,27 @@ int whmr_resize_coeffs(int in_w, int out_w, int in_h, int out_h, int32_t* coef, 
 int whmr_resize_normalize_frames(const uint8_t* frames, int F, int H, int W, int h, int w, const int32_t* coef, long coef_words, uint8_t* mid,
                                  long mid_bytes, float* out, uint8_t* out_u8, const float* mean3, const float* std3, void* stream);
 
+/* ---- clip inference, output side (csrc/smooth.hip): temporal smoothing of tracked persons -- what the --smooth / --min_cutoff / --beta flags of
+ * demo/whmr_demo.py:135-144 ask for (the reference parses them and never filters).  A one-euro filter per track with time counted in FRAMES: the
+ * scalar recurrence is the reference tree's OneEuroFilter (models/ViTPose/mmpose/core/post_processing/one_euro_filter.py:59-102) with fps = d_cutoff
+ * and t_e = the frame gap; rotations are filtered on SO(3) (v = log(Rh^T R), the filtered velocity sets the cut-off, Rh = GramSchmidt(Rh exp(a v)):
+ * this package's form, the reference has none).  Per track 25 rotation channels (the 24 joints of local_pose and joint 0 of global_pose) and 14
+ * scalar channels (cam_t 3, focal 1, shape 10).
+ * Inputs: local_pose / global_pose [P, 72] angle-axis, cam_t [P, 3], focal [P], shape [P, 10].  The int32 device table names every row of the clip
+ * once: rows [P] = the n_tracked rows of the T tracks, track by track in frame order (CSR track_offsets [T + 1], track_offsets[T] = n_tracked),
+ * then the P - n_tracked untracked rows; gap [n_tracked] = frames since the track's previous sample, 0 = the track starts or restarts at this row;
+ * slot [T] = the track's row of the state arrays state_R [n_slots, 25, 9], state_w [n_slots, 25, 3], state_x / state_dx [n_slots, 14], which
+ * hold the last filtered sample (and filtered velocity) of the track on return and are read when a track's first gap of this call is not 0.
+ * Outputs: local_rotmat / global_rotmat [P, 24, 3, 3], local_pose_out / global_pose_out [P, 72], cam_t_out, focal_out, shape_out
+ * (global joints 1 .. 23 are the local ones).  A row of gap 0 and an untracked row leave with the bits they came in (rotmat = exp(pose)).  Outputs
+ * must not alias inputs.  One launch of T + P - n_tracked wavefronts on `stream`, no allocation, no atomics, bit-reproducible. */
+int whmr_track_smooth(const float* local_pose, const float* global_pose, const float* cam_t, const float* focal, const float* shape, int P,
+                      const int32_t* track_offsets, const int32_t* rows, const int32_t* gap, const int32_t* slot, int T, int n_tracked,
+                      float* state_R, float* state_w, float* state_x, float* state_dx, int n_slots,
+                      double min_cutoff, double beta, double d_cutoff,
+                      float* local_rotmat, float* global_rotmat, float* local_pose_out, float* global_pose_out, float* cam_t_out,
+                      float* focal_out, float* shape_out, void* stream);
+
 /* ---- backward-pass helpers of the ViT backbone (autograd of vit.py:61-140,313-332; driven by core/trainer.py:410-470).
  * The backward matrix products run on whmr_gemm_bf16 / whmr_gemm_f32: dX = dY.W uses W^T as the weight operand,
  * dW = dY^T.X uses the transposed activations -- both produced by whmr_transpose_cast. */

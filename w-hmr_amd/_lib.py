@@ -233,6 +233,8 @@ _SIGS = {
     'whmr_crop_normalize_frames': [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     'whmr_resize_coeffs': [_I, _I, _I, _I, _P, _L, _P],
     'whmr_resize_normalize_frames': [_P, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P],
+    'whmr_track_smooth': [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, C.c_double, C.c_double, C.c_double,
+                          _P, _P, _P, _P, _P, _P, _P, _P],
     'whmr_attention_fwd_train': [_P, _P, _P, _I, _I, _I, _I, _F, _P],
     'whmr_attention_bwd': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     'whmr_tz_conv1': [_P, _I, _P, _P, _I, _I, _I, _P],
@@ -1503,6 +1505,36 @@ def resize_normalize_frames(frames, h, w, coef, mid, out, out_u8, mean, std):
     m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     _check(lib().whmr_resize_normalize_frames(frames.data_ptr(), F_, H, W, h, w, coef.data_ptr(), coef.numel(), mid.data_ptr(), mid.numel(),
                                               out.data_ptr(), _ptr(out_u8), m3, s3, _stream()), 'whmr_resize_normalize_frames')
+    return out
+
+
+SMOOTH_ROT, SMOOTH_SCALAR = 25, 14          # channels per track of whmr_track_smooth (csrc/smooth.hip): rotations, scalars
+
+
+def track_smooth(local_pose, global_pose, cam_t, focal, shape, table, T, n_tracked, state, min_cutoff, beta, d_cutoff):
+    """One-euro smoothing of the tracked rows of a clip in one launch (include/whmr_hip.h: whmr_track_smooth).  table: the uploaded int32
+    [track_offsets (T + 1) | rows (P) | gap (n_tracked) | slot (T)]; state: (R [S, 25, 9], w [S, 25, 3], x [S, 14], dx [S, 14]), updated in place.
+    -> dict(local_rotmat, global_rotmat [P, 24, 3, 3], local_pose, global_pose [P, 72], cam_t, focal, shape) -- new tensors of the inputs' shapes"""
+    ins = (local_pose, global_pose, cam_t, focal, shape)
+    _dev(table, *(ins + tuple(state)))
+    P = local_pose.shape[0]
+    for t, n in zip(ins, (72, 72, 3, 1, 10)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == P * n, (tuple(t.shape), n)
+    S = state[0].shape[0]
+    for t, shp in zip(state, ((S, SMOOTH_ROT, 9), (S, SMOOTH_ROT, 3), (S, SMOOTH_SCALAR), (S, SMOOTH_SCALAR))):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == shp, tuple(t.shape)
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.numel() == 2 * T + 1 + P + n_tracked and 0 <= T <= min(n_tracked, S) and n_tracked <= P
+    base = table.data_ptr()
+    offsets, rows, gap, slot = base, base + 4 * (T + 1), base + 4 * (T + 1 + P), base + 4 * (T + 1 + P + n_tracked)
+    f32 = dict(dtype=torch.float32, device=local_pose.device)
+    out = dict(local_rotmat=torch.empty(P, 24, 3, 3, **f32), global_rotmat=torch.empty(P, 24, 3, 3, **f32), local_pose=torch.empty_like(local_pose),
+               global_pose=torch.empty_like(global_pose), cam_t=torch.empty_like(cam_t), focal=torch.empty_like(focal), shape=torch.empty_like(shape))
+    _check(lib().whmr_track_smooth(local_pose.data_ptr(), global_pose.data_ptr(), cam_t.data_ptr(), focal.data_ptr(), shape.data_ptr(), P,
+                                   offsets, rows, gap, slot, T, n_tracked, state[0].data_ptr(), state[1].data_ptr(), state[2].data_ptr(),
+                                   state[3].data_ptr(), S, float(min_cutoff), float(beta), float(d_cutoff),
+                                   out['local_rotmat'].data_ptr(), out['global_rotmat'].data_ptr(), out['local_pose'].data_ptr(),
+                                   out['global_pose'].data_ptr(), out['cam_t'].data_ptr(), out['focal'].data_ptr(), out['shape'].data_ptr(), _stream()),
+           'whmr_track_smooth')
     return out
 
 

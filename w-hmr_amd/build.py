@@ -22,7 +22,7 @@ def _stale(target, deps):
 # streams (the host pass prints "not a recognized feature" for the flag and ignores it).
 _NO_PK = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 NO_PACKED_FP32 = {f: _NO_PK for f in ('smpl_lbs.hip', 'smpl_fused.hip', 'geometry.hip', 'iuv_loss.hip', 'maf_sampler.hip', 'rasterize.hip', 'vit_ops.hip',
-                                         'pose_eval.hip', 'mesh_render.hip', 'augment.hip', 'whmr_loss.hip', 'adam.hip', 'frames.hip')}
+                                         'pose_eval.hip', 'mesh_render.hip', 'augment.hip', 'whmr_loss.hip', 'adam.hip', 'frames.hip', 'smooth.hip')}
 if os.environ.get('WHMR_BUILD_PACKED_FP32', '0') == '1':                 # A/B
     NO_PACKED_FP32 = {}
 
@@ -31,13 +31,13 @@ def build(force=False, verbose=True):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip')))
     hdrs = glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(CSRC, '*.inc'))
-    c_header = os.path.join(os.path.dirname(HERE), 'include', 'whmr_hip.h')            # whmr_loss.hip, adam.hip and frames.hip take their structs from the C header
+    c_header = os.path.join(os.path.dirname(HERE), 'include', 'whmr_hip.h')            # whmr_loss.hip, adam.hip, frames.hip and smooth.hip include the C header
     objdir = os.path.join(HERE, 'build')
     os.makedirs(objdir, exist_ok=True)
     jobs = []
     for s in srcs:
         o = os.path.join(objdir, os.path.basename(s)[:-4] + '.o')
-        if force or _stale(o, [s] + hdrs + ([c_header] if os.path.basename(s) in ('whmr_loss.hip', 'adam.hip', 'frames.hip') else [])):
+        if force or _stale(o, [s] + hdrs + ([c_header] if os.path.basename(s) in ('whmr_loss.hip', 'adam.hip', 'frames.hip', 'smooth.hip') else [])):
             jobs.append((s, o))
 
     def cc(job):

@@ -12,6 +12,11 @@ are a few dozen floats computed on the host.
 
 For a clip two launches prepare everything: ``crop_persons_frames`` (all patches of all frames) and ``full_image_input_pillow`` (the camera input of
 all frames, Pillow's 8-bit bilinear resize bit for bit); the camera model runs at batch F and ``frame_index`` hands each person their frame's camera.
+
+    sm = TrackSmoother(model);  out = infer_clip(model, frames, dets_per_frame, track_ids=ids_per_frame, smoother=sm)
+
+With a tracker's ids the rows of one person are linked over the frames (and over successive clips) and smoothed by a one-euro filter on the device
+(``whmr_track_smooth``: one launch), and the vertices are recomputed from the smoothed pose and shape: what --smooth of demo/whmr_demo.py:135-144 asks for.
 """
 import math
 
@@ -226,17 +231,21 @@ def _clip_result(out, kw, P):
 
 
 @torch.no_grad()
-def infer_clip(model, frames, dets_per_frame, with_full_image=True, pad_to=None):
+def infer_clip(model, frames, dets_per_frame, with_full_image=True, pad_to=None, track_ids=None, smoother=None):
     """All persons of all frames of a clip in ONE model call.  frames: list of uint8 [H_i, W_i, 3] RGB frames (device tensors or numpy) or one
     [F, H, W, 3] tensor; dets_per_frame: per frame its [(c_x, c_y, w, h), ...], possibly empty.  Returns the vis_dict of WHMR.forward with one row per
     person (frame order, then detection order) plus ``frame_index`` int64 [P]; None for a clip without any detection.  With with_full_image the
     camera model runs once per FRAME (batch F, Pillow-exact input) and all frames must have one size (ValueError otherwise).  pad_to=k pads the
-    person batch to the next multiple of k by repeating the last detection; every output is sliced back to P rows."""
+    person batch to the next multiple of k by repeating the last detection; every output is sliced back to P rows.
+    smoother (a TrackSmoother) with track_ids (per frame one id per detection, None = untracked): the rows of each id are smoothed over time, across
+    successive calls too; the host table is decided (and its ValueErrors raised) before anything is launched."""
+    plan = _smoothing_plan(smoother, track_ids, dets_per_frame)
     prep = prepare_clip(frames, dets_per_frame, with_full_image, pad_to)
     if prep is None:
         return None
     kw, P = prep
-    return _clip_result(model(**_clip_call(kw)), kw, P)
+    out = _clip_result(model(**_clip_call(kw)), kw, P)
+    return out if plan is None else smoother.run(out, plan)
 
 
 class ClipPipeline:
@@ -244,14 +253,18 @@ class ClipPipeline:
     (two launches per clip) stays outside the graph, as in FramePipeline.  person_bucket: the person batch is padded to its next multiple, so clips of
     similar size share a graph.  With ``renderer`` (utils.renderer_cam.MeshRenderer) the call returns (vis_dict, [F overlay images]): one
     ``render_frame`` launch group per frame over that frame's rows, behind the replayed graph on the same stream, no host sync; a frame without
-    detections comes back as a copy of itself."""
+    detections comes back as a copy of itself.  With ``smoother`` (a TrackSmoother) and per-call ``track_ids`` the smoothing stage (one filter launch +
+    two SMPL calls) runs behind the replayed graph on the same stream, outside the graph -- its table changes per clip, like the input preparation --
+    and the renderer draws the smoothed rows; the padding rows never enter a track."""
 
-    def __init__(self, model, with_full_image=True, person_bucket=8, renderer=None):
+    def __init__(self, model, with_full_image=True, person_bucket=8, renderer=None, smoother=None):
         self.model, self.with_full_image, self.person_bucket, self.renderer, self._graphs = model, with_full_image, person_bucket, renderer, {}
+        self.smoother = smoother
 
     @torch.no_grad()
-    def __call__(self, frames, dets_per_frame):
+    def __call__(self, frames, dets_per_frame, track_ids=None):
         from .graph import GraphedForward
+        plan = _smoothing_plan(self.smoother, track_ids, dets_per_frame)
         prep = prepare_clip(frames, dets_per_frame, self.with_full_image, self.person_bucket, want_frames=self.renderer is not None)
         if prep is None:
             return None
@@ -262,6 +275,8 @@ class ClipPipeline:
         if g is None:
             g = self._graphs[key] = GraphedForward(self.model, **call)
         out = _clip_result(g(**call), kw, P)
+        if plan is not None:
+            out = self.smoother.run(out, plan)
         if self.renderer is None:
             return out
         images, row = [], 0
@@ -271,3 +286,149 @@ class ClipPipeline:
                           if n else frame.clone())
             row += n
         return out, images
+
+
+# ----------------------------------------------------------------------------- temporal smoothing of tracked persons
+def _smoothing_plan(smoother, track_ids, dets_per_frame):
+    """the host half of the smoothing stage of a clip call, before anything is launched: None without smoother / track_ids"""
+    if track_ids is None:
+        return None
+    if smoother is None:
+        raise ValueError('track_ids need a smoother (TrackSmoother)')
+    return smoother.plan_clip(dets_per_frame, track_ids)
+
+
+class SmoothPlan:
+    """What one smoothing call will do, decided on the host: the int32 table of whmr_track_smooth as numpy arrays (``offsets`` [T + 1], ``rows`` [P],
+    ``gap`` [n_tracked], ``slot`` [T]; ``ids``: the T track ids in table order) and the host state the call leaves behind (``commit``)."""
+
+    def __init__(self, offsets, rows, gap, slot, ids, commit):
+        self.offsets, self.rows, self.gap, self.slot, self.ids, self.commit = offsets, rows, gap, slot, ids, commit
+        self.P, self.T, self.n_tracked = len(rows), len(slot), len(gap)
+
+    def table(self):
+        return np.concatenate([self.offsets, self.rows, self.gap, self.slot]).astype(np.int32)
+
+
+class TrackSmoother:
+    """One-euro smoothing of tracked persons over the frames of a clip and across clips (--smooth / --min_cutoff / --beta of demo/whmr_demo.py:135-144;
+    the reference parses the flags and never filters).  Time is counted in frames.  Per track the 24 local joint rotations and the global root
+    rotation are filtered on SO(3), ``pred_cam_t``, ``focal_length`` and ``shape`` as scalars (``whmr_track_smooth``, csrc/smooth.hip: one launch);
+    ``local_smpl_vertices`` / ``smpl_vertices`` are recomputed by the model's own SMPL from the smoothed shape and rotations; ``cam_rotmat`` and
+    ``render_rotmat`` are per-frame camera outputs and pass through.
+
+    The host never reads device memory: it keeps track id -> state slot and each track's last absolute frame number, and a running frame counter
+    that advances by F per clip call.  A track unseen for more than ``max_gap`` frames restarts; ``reset(track_id)`` frees a slot.  ValueError, before
+    anything is launched: one id twice in one frame, more live tracks than ``max_tracks``.  ``model`` may be None for host-side planning only."""
+
+    def __init__(self, model, min_cutoff=0.004, beta=1.0, d_cutoff=1.0, max_tracks=64, max_gap=30):
+        if not (0 < min_cutoff <= 1e30 and 0 <= beta <= 1e30 and 0 < d_cutoff <= 1e30):
+            raise ValueError('min_cutoff and d_cutoff are positive, beta is not negative (got %r, %r, %r)' % (min_cutoff, beta, d_cutoff))
+        if max_tracks < 1 or max_gap < 1:
+            raise ValueError('max_tracks and max_gap are at least 1 (got %r, %r)' % (max_tracks, max_gap))
+        self.model, self.min_cutoff, self.beta, self.d_cutoff = model, float(min_cutoff), float(beta), float(d_cutoff)
+        self.max_tracks, self.max_gap = int(max_tracks), int(max_gap)
+        self.frame_counter = 0                      # absolute number of the next clip's first frame
+        self._slots, self._last = {}, {}            # track id -> state slot, track id -> absolute frame number of its last sample
+        self._state = None                          # device arrays, allocated with the first launch
+        self.rotmats = None                         # (local_rotmat, global_rotmat) [P, 24, 3, 3] of the last call
+
+    def reset(self, track_id=None):
+        """forget one track (its slot is free again; the id starts a new track when it returns) or, without an id, all tracks and the frame counter"""
+        if track_id is None:
+            self._slots, self._last, self.frame_counter = {}, {}, 0
+        else:
+            self._slots.pop(track_id, None)
+            self._last.pop(track_id, None)
+
+    # ---- host
+    def plan(self, track_ids, frame_numbers):
+        """-> SmoothPlan for rows with these ids (None: untracked) at these absolute frame numbers.  Changes nothing: ``run`` commits the plan."""
+        ids, frames = list(track_ids), [int(f) for f in frame_numbers]
+        if len(ids) != len(frames):
+            raise ValueError('%d track ids but %d frame numbers' % (len(ids), len(frames)))
+        tracks = {}                                                               # id -> [(frame, row)], ids in order of first appearance
+        for row, (i, f) in enumerate(zip(ids, frames)):
+            if i is not None:
+                tracks.setdefault(i, []).append((f, row))
+        slots, last = dict(self._slots), dict(self._last)
+        free = sorted(set(range(self.max_tracks)) - set(slots.values()), reverse=True)
+        offsets, rows, gap, slot = [0], [], [], []
+        for i, samples in tracks.items():
+            samples.sort()
+            for (f0, _), (f1, _) in zip(samples, samples[1:]):
+                if f0 == f1:
+                    raise ValueError('track id %r appears twice in frame %d' % (i, f0))
+            if i in last and samples[0][0] <= last[i]:
+                raise ValueError('track id %r: frame %d does not come after its last sample (frame %d)' % (i, samples[0][0], last[i]))
+            if i not in slots:
+                if not free:
+                    raise ValueError('more than max_tracks = %d live tracks (id %r); reset(track_id) frees a slot' % (self.max_tracks, i))
+                slots[i] = free.pop()
+            prev = last.get(i)
+            for f, row in samples:
+                d = 0 if prev is None else f - prev
+                gap.append(d if d <= self.max_gap else 0)                          # unseen for more than max_gap frames: the track restarts
+                rows.append(row)
+                prev = f
+            last[i] = prev
+            slot.append(slots[i])
+            offsets.append(len(rows))
+        rows += [row for row, i in enumerate(ids) if i is None]
+        i32 = lambda v: np.asarray(v, dtype=np.int32).reshape(-1)
+        return SmoothPlan(i32(offsets), i32(rows), i32(gap), i32(slot), list(tracks), (slots, last, None))
+
+    def plan_clip(self, dets_per_frame, track_ids):
+        """``plan`` for a clip call: track_ids mirrors dets_per_frame; frame f of the clip is absolute frame frame_counter + f, and the counter
+        advances by the number of frames when the plan runs (a clip without any detection advances it at once)."""
+        if len(track_ids) != len(dets_per_frame) or any(len(t) != len(d) for t, d in zip(track_ids, dets_per_frame)):
+            raise ValueError('track_ids must mirror dets_per_frame: one id (or None) per detection')
+        flat = [i for t in track_ids for i in t]
+        frames = [self.frame_counter + f for f, t in enumerate(track_ids) for _ in t]
+        p = self.plan(flat, frames)
+        p.commit = p.commit[:2] + (self.frame_counter + len(dets_per_frame),)
+        if not flat:
+            self._commit(p)
+        return p
+
+    def _commit(self, plan):
+        slots, last, counter = plan.commit
+        self._slots, self._last = slots, last
+        if counter is not None:
+            self.frame_counter = counter
+
+    # ---- device
+    def _device_state(self, dev):
+        if self._state is None or self._state[0].device != dev:
+            S, f32 = self.max_tracks, dict(dtype=torch.float32, device=dev)
+            self._state = (torch.zeros(S, L.SMOOTH_ROT, 9, **f32), torch.zeros(S, L.SMOOTH_ROT, 3, **f32), torch.zeros(S, L.SMOOTH_SCALAR, **f32),
+                           torch.zeros(S, L.SMOOTH_SCALAR, **f32))
+        return self._state
+
+    @torch.no_grad()
+    def run(self, vis_dict, plan):
+        """the device half: upload the table (one non-blocking copy from pinned memory), one filter launch, two SMPL calls.  Returns a new dictionary
+        with the keys of ``vis_dict`` and the smoothed tensors in place; ``self.rotmats`` keeps the smoothed (local, global) rotation matrices."""
+        local_pose = vis_dict['local_pose']
+        if not local_pose.is_cuda:
+            raise RuntimeError('TrackSmoother runs on a HIP device only (no CPU fallback)')
+        if local_pose.shape[0] != plan.P:
+            raise ValueError('the plan is for %d rows, the result has %d' % (plan.P, local_pose.shape[0]))
+        dev = local_pose.device
+        state = self._device_state(dev)
+        self._commit(plan)
+        table = torch.from_numpy(plan.table()).pin_memory().to(dev, non_blocking=True)
+        c = lambda k: vis_dict[k].float().contiguous()
+        sm = L.track_smooth(c('local_pose'), c('global_pose'), c('pred_cam_t'), c('focal_length'), c('shape'), table, plan.T, plan.n_tracked, state,
+                            self.min_cutoff, self.beta, self.d_cutoff)
+        smpl = self.model.regressor[0].smpl
+        out = dict(vis_dict)
+        out.update(local_pose=sm['local_pose'], global_pose=sm['global_pose'], pred_cam_t=sm['cam_t'], focal_length=sm['focal'], shape=sm['shape'],
+                   local_smpl_vertices=smpl.run(sm['shape'], sm['local_rotmat']).vertices,
+                   smpl_vertices=smpl.run(sm['shape'], sm['global_rotmat']).vertices)
+        self.rotmats = (sm['local_rotmat'], sm['global_rotmat'])
+        return out
+
+    def smooth(self, vis_dict, track_ids, frame_numbers):
+        """the stage on its own: rows of ``vis_dict`` with these track ids (None: untracked) at these absolute frame numbers"""
+        return self.run(vis_dict, self.plan(track_ids, frame_numbers))
