@@ -730,6 +730,26 @@ int whmr_mesh_render(const float* verts, int P, int V, const int32_t* faces, int
                      const uint8_t* frame, int H, int W, int per_person, float base_r, float base_g, float base_b, float ambient, float k_d,
                      float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, uint8_t* out, float* color_out, int32_t* face_out,
                      float* depth_out, void* stream);
+/* The draw-list form (same file, same device code per vertex, face and pixel -- the same bits): D mesh instances ("draws") into NI target images in
+ * the same three launches: the overlays of a whole clip, its per-person images, the strips of render_image_group.  Two DEVICE tables, packed by the
+ * host as little-endian rows of fixed size (byte offsets; the layout is asserted in csrc/mesh_render.hip and restated by whmr_amd._lib.
+ * RENDER_IMAGE_DTYPE / RENDER_DRAW_DTYPE):
+ *   images, NI rows of 56 bytes:  0 frame (const uint8_t*, background, null = black)   8 out (uint8_t*)   16 frame_row_stride   24 out_row_stride
+ *     (int64, bytes: pixel (y, x) at base + y * stride + 3 x, so a target can be one panel of a strip and a background a row-strided view)
+ *     32 pix_off (int64: the image's first element of the packed per-pixel planes)   40 H   44 W (int32)   48 cx   52 cy (float, camera centre)
+ *   draws, D rows of 32 bytes:  0 row (int32: row of cam_t, focal and the vertex set)   4 verts_set (int32, 0: verts0, 1: verts1)   8 image (int32)
+ *     12 side_cos   16 side_sin (float, of the draw's sideview_angle)   20 .. 31 reserved
+ * verts0, verts1 (or null) [R, V, 3]; cam_t [R, 3]; focal [R, 2]; faces, vf_ptr, vf_idx, rot (one for all draws), znear and the shading constants as
+ * above; total_pixels = sum of H * W = the length of the packed planes.  Scratch: scr, nrm [D, V, 3] fp32, zbuf [total_pixels] uint64.  Optional, or
+ * null: color_out [total_pixels, 3] fp32, face_out [total_pixels] int32, depth_out [total_pixels] fp32.  The global face id is draw * F + face (D * F <
+ * 2^31, hipErrorInvalidValue otherwise; NI <= 65535); draws that name one image share its depth buffer and ties go to the smaller id, the earlier
+ * draw: with a frame's persons listed in row order a shared image is decided exactly as whmr_mesh_render decides it.  A draw whose row, verts_set or
+ * image is out of range is not drawn.  D = 0 copies the backgrounds.  Three launches, no allocation, no synchronisation; bit-reproducible. */
+int whmr_mesh_render_draws(const float* verts0, const float* verts1, int R, int V, const int32_t* faces, int F, const int32_t* vf_ptr,
+                           const int32_t* vf_idx, const float* cam_t, const float* focal, const void* draws, int D, const void* images, int NI,
+                           long total_pixels, const float* rot, float znear, float base_r, float base_g, float base_b, float ambient, float k_d,
+                           float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, float* color_out, int32_t* face_out, float* depth_out,
+                           void* stream);
 
 /* ---- training input side (csrc/augment.hip): the sample-making of BaseDataset.__getitem__ (datasets/base_dataset.py:249-384) for a whole batch --
  * rgb_processing (:183-207) over utils/imutils.py:crop (:54-88: integer box, skimage rotate, Pillow bicubic resize), Normalize and the

@@ -8,6 +8,7 @@ import math
 import os
 import struct
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -282,6 +283,8 @@ _SIGS = {
     'whmr_iuv_rasterize': [_P, _I, _I, _P, _I, _P, _I, _P, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     'whmr_mesh_render': [_P, _I, _I, _P, _I, _P, _P, _P, _P, _F, _F, _P, _F, _F, _F, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
                          _P, _P],
+    'whmr_mesh_render_draws': [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
+                               _P],
     'whmr_iuv_losses': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     'whmr_iuv_losses_bwd': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _L, _P],
     'whmr_train_losses_workspace': [C.POINTER(_WhmrLossArgs), C.POINTER(C.c_long)],
@@ -903,6 +906,77 @@ def mesh_render(verts, faces, vf_ptr, vf_idx, cam_t, focal, center, frame, size,
         res['depth'] = sq(dep)
     if 'screen' in want:
         res['screen'] = scr.clone()
+    return res
+
+
+# rows of the two device tables of whmr_mesh_render_draws (include/whmr_hip.h; asserted field by field in csrc/mesh_render.hip): numpy record types, so
+# the host fills whole columns at once
+RENDER_IMAGE_DTYPE = np.dtype({'names': ['frame', 'out', 'frame_row_stride', 'out_row_stride', 'pix_off', 'H', 'W', 'cx', 'cy'],
+                               'formats': ['<u8', '<u8', '<i8', '<i8', '<i8', '<i4', '<i4', '<f4', '<f4'],
+                               'offsets': [0, 8, 16, 24, 32, 40, 44, 48, 52], 'itemsize': 56})
+RENDER_DRAW_DTYPE = np.dtype({'names': ['row', 'verts_set', 'image', 'side_cos', 'side_sin', 'reserved'],
+                              'formats': ['<i4', '<i4', '<i4', '<f4', '<f4', ('<i4', (3,))], 'offsets': [0, 4, 8, 12, 16, 20], 'itemsize': 32})
+_draw_ws = {}
+
+
+def _draw_workspace(dev, n_vert_floats, n_pixels):
+    """(scr, nrm, zbuf) of whmr_mesh_render_draws per (device, stream), grow-only: a buffer that became too small is replaced by one of at least twice
+    its size and kept alive, so a call captured in a graph stays valid while larger eager calls run beside it."""
+    ws = _draw_ws.setdefault((dev, torch.cuda.current_stream(dev).cuda_stream), {'scr': None, 'nrm': None, 'zbuf': None, 'retired': []})
+    for k, need, dtype in (('scr', n_vert_floats, torch.float32), ('nrm', n_vert_floats, torch.float32), ('zbuf', n_pixels, torch.int64)):
+        if ws[k] is None or ws[k].numel() < need:
+            if ws[k] is not None:
+                ws['retired'].append(ws[k])
+            ws[k] = torch.empty(max(need, 2 * ws[k].numel() if ws[k] is not None else 1), dtype=dtype, device=dev)
+    return ws['scr'], ws['nrm'], ws['zbuf']
+
+
+def mesh_render_draws(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, draws, n_draws, images, n_images, total_pixels, color, rot=None, znear=0.05,
+                      ambient=0.3, k_d=4 * (1 - 0.2) * (1 - 0.04) / math.pi, light=(0.0, 0.0, 1.0), want=()):
+    """Draw-list form of ``mesh_render`` (include/whmr_hip.h: whmr_mesh_render_draws): ``n_draws`` mesh instances into ``n_images`` target images in
+    three launches.  draws / images: the two tables as uint8 DEVICE tensors of RENDER_DRAW_DTYPE / RENDER_IMAGE_DTYPE rows -- nothing is packed here, and
+    the output images are the ones the image table points at (the caller keeps them alive).  verts0, verts1 (or None) [R, V, 3], cam_t [R, 3], focal
+    [R, 2] fp32.  Returns a dict of the packed per-pixel planes asked for in ``want`` ('color' [total_pixels, 3] fp32, 'face' [total_pixels] int32 =
+    draw * F + face or -1, 'depth' [total_pixels] fp32; an image's part starts at its pix_off) and 'screen' [D, V, 3].  The scratch is kept per
+    (device, stream) and only grows; the planes are fresh."""
+    _dev(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, draws, images)
+    R, V = verts0.shape[0], verts0.shape[1]
+    F = faces.shape[0]
+    D, NI, total = int(n_draws), int(n_images), int(total_pixels)
+    for v in (verts0, verts1):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == (R, V, 3))
+    assert cam_t.dtype == torch.float32 and cam_t.is_contiguous() and tuple(cam_t.shape) == (R, 3)
+    assert focal.dtype == torch.float32 and focal.is_contiguous() and tuple(focal.shape) == (R, 2)
+    assert faces.dtype == torch.int32 and faces.is_contiguous() and faces.dim() == 2 and faces.shape[1] == 3
+    assert vf_ptr.dtype == torch.int32 and vf_ptr.is_contiguous() and vf_ptr.numel() == V + 1
+    assert vf_idx.dtype == torch.int32 and vf_idx.is_contiguous() and vf_idx.numel() == 3 * F
+    assert draws.dtype == torch.uint8 and draws.is_contiguous() and draws.numel() == D * RENDER_DRAW_DTYPE.itemsize
+    assert images.dtype == torch.uint8 and images.is_contiguous() and images.numel() == NI * RENDER_IMAGE_DTYPE.itemsize
+    assert R >= 1 and D >= 0 and 1 <= NI <= 65535 and total >= 1 and D * F < 2 ** 31
+    unknown = set(want) - {'color', 'face', 'depth', 'screen'}
+    assert not unknown, 'unknown outputs %s' % sorted(unknown)
+    dev = verts0.device
+    scr, nrm, zbuf = _draw_workspace(dev, max(D, 1) * V * 3, total)
+    res = {}
+    if 'color' in want:
+        res['color'] = torch.empty(total, 3, dtype=torch.float32, device=dev)
+    if 'face' in want:
+        res['face'] = torch.empty(total, dtype=torch.int32, device=dev)
+    if 'depth' in want:
+        res['depth'] = torch.empty(total, dtype=torch.float32, device=dev)
+    rot_c = None
+    if rot is not None:
+        r = [float(v) for row in rot for v in row]
+        assert len(r) == 9
+        rot_c = (C.c_float * 9)(*r)
+    lx, ly, lz = (float(v) for v in light)
+    _check(lib().whmr_mesh_render_draws(verts0.data_ptr(), _ptr(verts1), R, V, faces.data_ptr(), F, vf_ptr.data_ptr(), vf_idx.data_ptr(), cam_t.data_ptr(),
+                                        focal.data_ptr(), draws.data_ptr(), D, images.data_ptr(), NI, total,
+                                        C.cast(rot_c, C.c_void_p) if rot_c is not None else None, float(znear), float(color[0]), float(color[1]),
+                                        float(color[2]), float(ambient), float(k_d), lx, ly, lz, scr.data_ptr(), nrm.data_ptr(), zbuf.data_ptr(),
+                                        _ptr(res.get('color')), _ptr(res.get('face')), _ptr(res.get('depth')), _stream()), 'whmr_mesh_render_draws')
+    if 'screen' in want:
+        res['screen'] = scr[:D * V * 3].view(D, V, 3).clone()
     return res
 
 

@@ -29,16 +29,11 @@
 
 struct mesh_cam { float cx, cy, sc, ss; int has_rot; float r[9]; };
 
-// Launch 1: z-buffer clear + one thread per (person, vertex): camera transform, projection, vertex normal.
-__global__ __launch_bounds__(256) void mesh_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, const int32_t* __restrict__ vf_ptr,
-                                                          const int32_t* __restrict__ vf_idx, const float* __restrict__ cam_t, const float* __restrict__ focal,
-                                                          float* __restrict__ scr, float* __restrict__ nrm, unsigned long long* __restrict__ zbuf, long npix,
-                                                          int P, int V, mesh_cam c) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx < npix) zbuf[idx] = ~0ull;
-    if (idx >= (long)P * V) return;
-    const int p = (int)(idx / V), v = (int)(idx - (long)p * V);
-    const float* vp = verts + (size_t)p * V * 3;
+// The vertex transform of launch 1, one code path for both entry points: vertex v of the mesh at vp (mesh frame) under camera c with translation t and
+// focal lengths fo -> its screen position (u, v, depth) and its world-frame smooth normal.
+__device__ __forceinline__ void mesh_vertex(const float* __restrict__ vp, int v, const int32_t* __restrict__ faces, const int32_t* __restrict__ vf_ptr,
+                                            const int32_t* __restrict__ vf_idx, const float* __restrict__ t, const float* __restrict__ fo, const mesh_cam& c,
+                                            float* __restrict__ scr, float* __restrict__ nrm) {
     // world: q = S D p,  S = [[c, 0, s], [0, 1, 0], [-s, 0, c]]
     const float x = vp[v * 3], y = -vp[v * 3 + 1], z = -vp[v * 3 + 2];
     const float qx = c.sc * x + c.ss * z, qy = y, qz = c.sc * z - c.ss * x;
@@ -48,10 +43,10 @@ __global__ __launch_bounds__(256) void mesh_vertex_kernel(const float* __restric
         py = (c.r[1] * qx + c.r[4] * qy) + c.r[7] * qz;
         pz = (c.r[2] * qx + c.r[5] * qy) + c.r[8] * qz;
     }
-    const float X = px + cam_t[p * 3], Y = cam_t[p * 3 + 1] - py, Z = cam_t[p * 3 + 2] - pz;
-    scr[idx * 3] = c.cx + focal[p * 2] * X / Z;
-    scr[idx * 3 + 1] = c.cy + focal[p * 2 + 1] * Y / Z;
-    scr[idx * 3 + 2] = Z;
+    const float X = px + t[0], Y = t[1] - py, Z = t[2] - pz;
+    scr[0] = c.cx + fo[0] * X / Z;
+    scr[1] = c.cy + fo[1] * Y / Z;
+    scr[2] = Z;
     float nx = 0.f, ny = 0.f, nz = 0.f;
     for (int k = vf_ptr[v]; k < vf_ptr[v + 1]; ++k) {
         const int32_t* f = faces + (size_t)vf_idx[k] * 3;
@@ -63,7 +58,19 @@ __global__ __launch_bounds__(256) void mesh_vertex_kernel(const float* __restric
     }
     const float inv = __builtin_amdgcn_rsqf(fmaxf((nx * nx + ny * ny) + nz * nz, 1e-30f));
     nx *= inv; ny = -ny * inv; nz = -nz * inv;                                    // D n
-    nrm[idx * 3] = c.sc * nx + c.ss * nz; nrm[idx * 3 + 1] = ny; nrm[idx * 3 + 2] = c.sc * nz - c.ss * nx;
+    nrm[0] = c.sc * nx + c.ss * nz; nrm[1] = ny; nrm[2] = c.sc * nz - c.ss * nx;
+}
+
+// Launch 1: z-buffer clear + one thread per (person, vertex): camera transform, projection, vertex normal.
+__global__ __launch_bounds__(256) void mesh_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, const int32_t* __restrict__ vf_ptr,
+                                                          const int32_t* __restrict__ vf_idx, const float* __restrict__ cam_t, const float* __restrict__ focal,
+                                                          float* __restrict__ scr, float* __restrict__ nrm, unsigned long long* __restrict__ zbuf, long npix,
+                                                          int P, int V, mesh_cam c) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < npix) zbuf[idx] = ~0ull;
+    if (idx >= (long)P * V) return;
+    const int p = (int)(idx / V), v = (int)(idx - (long)p * V);
+    mesh_vertex(verts + (size_t)p * V * 3, v, faces, vf_ptr, vf_idx, cam_t + p * 3, focal + p * 2, c, scr + idx * 3, nrm + idx * 3);
 }
 
 // Edge function of the oriented edge a -> b at p, evaluated from the lexicographically smaller end point (see the header): the explicit fma keeps
@@ -117,32 +124,42 @@ __device__ __forceinline__ void mesh_pixel(const mesh_tri& t, int x, int y, unsi
     if (__hip_atomic_load(z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(z, key);
 }
 
-__global__ __launch_bounds__(256) void mesh_faces_kernel(const float* __restrict__ scr, const int32_t* __restrict__ faces, unsigned long long* __restrict__ zbuf,
-                                                         int P, int V, int F, int H, int W, int per_person, float znear) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+// The face pass, one code path for both entry points.  ``tg`` names the targets: tg.image(p) = the image that mesh instance p is drawn into (negative:
+// not drawn), tg.target(img) = that image's size and its first element of the z-buffer.  The wave walk asks for the target of the OWNER lane's image:
+// one wave can hold faces of instances whose images differ in size and z-buffer base.
+struct mesh_target { int H, W; long off; };
+template <class Targets>
+__device__ __forceinline__ void mesh_faces(const float* __restrict__ scr, const int32_t* __restrict__ faces, unsigned long long* __restrict__ zbuf, long idx,
+                                           long n_faces, int V, int F, float znear, const Targets& tg) {
     const int lane = threadIdx.x & 63;
     mesh_tri t;
     int x0 = 0, x1 = -1, y0 = 0, y1 = -1, img = 0;
     unsigned gid = 0;
     bool ok = false;
-    if (idx < (long)P * F) {
+    if (idx < n_faces) {
         const int p = (int)(idx / F), f = (int)(idx - (long)p * F);
-        gid = (unsigned)idx; img = per_person ? p : 0;
-        const float* s = scr + (size_t)p * V * 3;
+        gid = (unsigned)idx; img = tg.image(p);
+        if (img >= 0) {
+            const mesh_target g = tg.target(img);
+            const int H = g.H, W = g.W;
+            const float* s = scr + (size_t)p * V * 3;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float* vp = s + (size_t)faces[f * 3 + k] * 3;
-            t.v[3 * k] = vp[0]; t.v[3 * k + 1] = vp[1]; t.v[3 * k + 2] = vp[2];
-        }
-        const float xmin = fminf(t.v[0], fminf(t.v[3], t.v[6])), xmax = fmaxf(t.v[0], fmaxf(t.v[3], t.v[6]));
-        const float ymin = fminf(t.v[1], fminf(t.v[4], t.v[7])), ymax = fmaxf(t.v[1], fmaxf(t.v[4], t.v[7]));
-        // every comparison is false for a NaN, but fminf / fmaxf skip one: the sum of the screen coordinates is looked at as well (inf - inf: dropped too)
-        const float any = ((t.v[0] + t.v[1]) + (t.v[3] + t.v[4])) + (t.v[6] + t.v[7]);
-        ok = t.v[2] > znear && t.v[5] > znear && t.v[8] > znear && any == any && xmax >= 0.5f && ymax >= 0.5f && xmin <= (float)W - 0.5f &&
-             ymin <= (float)H - 0.5f;
-        if (ok) {                                                                 // centres i + 0.5 in [min, max]; clamped as floats, so the casts are in range
-            x0 = (int)fmaxf(ceilf(xmin - 0.5f), 0.f); x1 = (int)fminf(floorf(xmax - 0.5f), (float)(W - 1));
-            y0 = (int)fmaxf(ceilf(ymin - 0.5f), 0.f); y1 = (int)fminf(floorf(ymax - 0.5f), (float)(H - 1));
+            for (int k = 0; k < 3; ++k) {
+                const float* vp = s + (size_t)faces[f * 3 + k] * 3;
+                t.v[3 * k] = vp[0]; t.v[3 * k + 1] = vp[1]; t.v[3 * k + 2] = vp[2];
+            }
+            const float xmin = fminf(t.v[0], fminf(t.v[3], t.v[6])), xmax = fmaxf(t.v[0], fmaxf(t.v[3], t.v[6]));
+            const float ymin = fminf(t.v[1], fminf(t.v[4], t.v[7])), ymax = fmaxf(t.v[1], fmaxf(t.v[4], t.v[7]));
+            // every comparison is false for a NaN, but fminf / fmaxf skip one: the sum of the screen coordinates is looked at as well (inf - inf: dropped too)
+            const float any = ((t.v[0] + t.v[1]) + (t.v[3] + t.v[4])) + (t.v[6] + t.v[7]);
+            ok = t.v[2] > znear && t.v[5] > znear && t.v[8] > znear && any == any && xmax >= 0.5f && ymax >= 0.5f && xmin <= (float)W - 0.5f &&
+                 ymin <= (float)H - 0.5f;
+            if (ok) {                                                             // centres i + 0.5 in [min, max]; clamped as floats, so the casts are in range
+                x0 = (int)fmaxf(ceilf(xmin - 0.5f), 0.f); x1 = (int)fminf(floorf(xmax - 0.5f), (float)(W - 1));
+                y0 = (int)fmaxf(ceilf(ymin - 0.5f), 0.f); y1 = (int)fminf(floorf(ymax - 0.5f), (float)(H - 1));
+            }
+        } else {
+            img = 0;
         }
     }
     if (!ok) {
@@ -153,9 +170,10 @@ __global__ __launch_bounds__(256) void mesh_faces_kernel(const float* __restrict
     const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
     const int npx = (bw > 0 && bh > 0 && ok) ? bw * bh : 0;
     if (npx > 0 && npx <= MESH_SMALL) {
-        unsigned long long* z0 = zbuf + (size_t)img * H * W;
+        const mesh_target g = tg.target(img);
+        unsigned long long* z0 = zbuf + g.off;
         for (int y = y0; y <= y1; ++y)
-            for (int x = x0; x <= x1; ++x) mesh_pixel(t, x, y, gid, z0, W);
+            for (int x = x0; x <= x1; ++x) mesh_pixel(t, x, y, gid, z0, g.W);
     }
     unsigned long long big = __ballot(npx > MESH_SMALL);
     while (big) {
@@ -167,7 +185,8 @@ __global__ __launch_bounds__(256) void mesh_faces_kernel(const float* __restrict
         mesh_setup(u);                                                            // the same arithmetic on the same inputs: the owner lane's bits
         const int ux0 = __shfl(x0, L, 64), uy0 = __shfl(y0, L, 64), ux1 = __shfl(x1, L, 64), uy1 = __shfl(y1, L, 64);
         const unsigned ug = (unsigned)__shfl((int)gid, L, 64);
-        unsigned long long* z0 = zbuf + (size_t)__shfl(img, L, 64) * H * W;
+        const mesh_target g = tg.target(__shfl(img, L, 64));                      // the owner's image: its width and its z-buffer
+        unsigned long long* z0 = zbuf + g.off;
         // the box in 64-pixel tiles shaped after its height (64 x 1 ... 8 x 8), lane = pixel of the tile: no per-pixel index division
         const int uh = uy1 - uy0 + 1;
         const int lw = uh <= 1 ? 6 : uh <= 2 ? 5 : uh <= 4 ? 4 : 3;
@@ -176,12 +195,68 @@ __global__ __launch_bounds__(256) void mesh_faces_kernel(const float* __restrict
         for (int ty = uy0; ty <= uy1; ty += th)
             for (int tx = ux0; tx <= ux1; tx += tw) {
                 const int x = tx + lx, y = ty + ly;
-                if (x <= ux1 && y <= uy1) mesh_pixel(u, x, y, ug, z0, W);
+                if (x <= ux1 && y <= uy1) mesh_pixel(u, x, y, ug, z0, g.W);
             }
     }
 }
 
+struct mesh_frame_targets {                                                       // whmr_mesh_render: images of one size, one for all persons or one each
+    int H, W, per_person;
+    __device__ __forceinline__ int image(int p) const { return per_person ? p : 0; }
+    __device__ __forceinline__ mesh_target target(int img) const { return mesh_target{H, W, (long)img * H * W}; }
+};
+
+__global__ __launch_bounds__(256) void mesh_faces_kernel(const float* __restrict__ scr, const int32_t* __restrict__ faces, unsigned long long* __restrict__ zbuf,
+                                                         int P, int V, int F, int H, int W, int per_person, float znear) {
+    mesh_faces(scr, faces, zbuf, (long)blockIdx.x * 256 + threadIdx.x, (long)P * F, V, F, znear, mesh_frame_targets{H, W, per_person});
+}
+
 struct mesh_shade { float r, g, b, ambient, kd, lx, ly, lz; };
+struct mesh_sample { int gid; float c0, c1, c2, depth; bool hit; };
+
+// The resolve of one pixel, one code path for both entry points: the z-buffer's winner at pixel (x, y) -> global face id, shaded colour and depth.
+__device__ __forceinline__ mesh_sample mesh_resolve(unsigned long long key, int x, int y, const float* __restrict__ scr, const float* __restrict__ nrm,
+                                                    const int32_t* __restrict__ faces, int V, int F, const mesh_shade& m) {
+    mesh_sample o{-1, 0.f, 0.f, 0.f, 0.f, false};
+    if (key == ~0ull) return o;
+    o.gid = (int)(key & 0xffffffffu);
+    const int p = o.gid / F, f = o.gid - p * F;
+    const float* s = scr + (size_t)p * V * 3;
+    const float* n = nrm + (size_t)p * V * 3;
+    const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+    mesh_tri t;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { t.v[k] = s[(size_t)i0 * 3 + k]; t.v[3 + k] = s[(size_t)i1 * 3 + k]; t.v[6 + k] = s[(size_t)i2 * 3 + k]; }
+    mesh_setup(t);
+    float b0, b1, b2;
+    o.hit = mesh_bary(t, x + 0.5f, y + 0.5f, b0, b1, b2, o.depth);                // true: the face pass took the same path
+    if (o.hit) {
+        const float nx = (b0 * n[(size_t)i0 * 3] + b1 * n[(size_t)i1 * 3]) + b2 * n[(size_t)i2 * 3];
+        const float ny = (b0 * n[(size_t)i0 * 3 + 1] + b1 * n[(size_t)i1 * 3 + 1]) + b2 * n[(size_t)i2 * 3 + 1];
+        const float nz = (b0 * n[(size_t)i0 * 3 + 2] + b1 * n[(size_t)i1 * 3 + 2]) + b2 * n[(size_t)i2 * 3 + 2];
+        const float inv = __builtin_amdgcn_rsqf(fmaxf((nx * nx + ny * ny) + nz * nz, 1e-30f));
+        const float ndl = fmaxf(((nx * m.lx + ny * m.ly) + nz * m.lz) * inv, 0.f);
+        const float lum = m.ambient + m.kd * ndl;
+        o.c0 = __builtin_amdgcn_fmed3f(m.r * lum, 0.f, 1.f); o.c1 = __builtin_amdgcn_fmed3f(m.g * lum, 0.f, 1.f); o.c2 = __builtin_amdgcn_fmed3f(m.b * lum, 0.f, 1.f);
+    } else {
+        o.gid = -1; o.depth = 0.f;
+    }
+    return o;
+}
+// the pixel's bytes (o: the output pixel, fr: the background pixel or null = black) and its entries `at` of the optional planes
+__device__ __forceinline__ void mesh_store(const mesh_sample& s, uint8_t* __restrict__ o, const uint8_t* __restrict__ fr, long at, float* __restrict__ color_out,
+                                           int32_t* __restrict__ face_out, float* __restrict__ depth_out) {
+    if (s.hit) {
+        o[0] = (uint8_t)rintf(255.f * s.c0); o[1] = (uint8_t)rintf(255.f * s.c1); o[2] = (uint8_t)rintf(255.f * s.c2);
+    } else if (fr) {
+        o[0] = fr[0]; o[1] = fr[1]; o[2] = fr[2];
+    } else {
+        o[0] = 0; o[1] = 0; o[2] = 0;
+    }
+    if (color_out) { color_out[at * 3] = s.c0; color_out[at * 3 + 1] = s.c1; color_out[at * 3 + 2] = s.c2; }
+    if (face_out) face_out[at] = s.gid;
+    if (depth_out) depth_out[at] = s.depth;
+}
 
 // Launch 3: one thread per pixel of every output image.
 __global__ __launch_bounds__(256) void mesh_resolve_kernel(const float* __restrict__ scr, const float* __restrict__ nrm, const int32_t* __restrict__ faces,
@@ -193,46 +268,7 @@ __global__ __launch_bounds__(256) void mesh_resolve_kernel(const float* __restri
     if (idx >= NI * plane) return;
     const long r = idx % plane;
     const int y = (int)(r / W), x = (int)(r - (long)y * W);
-    const unsigned long long key = zbuf[idx];
-    int gid = -1;
-    float c0 = 0.f, c1 = 0.f, c2 = 0.f, depth = 0.f;
-    bool hit = false;
-    if (key != ~0ull) {
-        gid = (int)(key & 0xffffffffu);
-        const int p = gid / F, f = gid - p * F;
-        const float* s = scr + (size_t)p * V * 3;
-        const float* n = nrm + (size_t)p * V * 3;
-        const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-        mesh_tri t;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { t.v[k] = s[(size_t)i0 * 3 + k]; t.v[3 + k] = s[(size_t)i1 * 3 + k]; t.v[6 + k] = s[(size_t)i2 * 3 + k]; }
-        mesh_setup(t);
-        float b0, b1, b2;
-        hit = mesh_bary(t, x + 0.5f, y + 0.5f, b0, b1, b2, depth);                // true: the face pass took the same path
-        if (hit) {
-            const float nx = (b0 * n[(size_t)i0 * 3] + b1 * n[(size_t)i1 * 3]) + b2 * n[(size_t)i2 * 3];
-            const float ny = (b0 * n[(size_t)i0 * 3 + 1] + b1 * n[(size_t)i1 * 3 + 1]) + b2 * n[(size_t)i2 * 3 + 1];
-            const float nz = (b0 * n[(size_t)i0 * 3 + 2] + b1 * n[(size_t)i1 * 3 + 2]) + b2 * n[(size_t)i2 * 3 + 2];
-            const float inv = __builtin_amdgcn_rsqf(fmaxf((nx * nx + ny * ny) + nz * nz, 1e-30f));
-            const float ndl = fmaxf(((nx * m.lx + ny * m.ly) + nz * m.lz) * inv, 0.f);
-            const float lum = m.ambient + m.kd * ndl;
-            c0 = __builtin_amdgcn_fmed3f(m.r * lum, 0.f, 1.f); c1 = __builtin_amdgcn_fmed3f(m.g * lum, 0.f, 1.f); c2 = __builtin_amdgcn_fmed3f(m.b * lum, 0.f, 1.f);
-        } else {
-            gid = -1; depth = 0.f;
-        }
-    }
-    uint8_t* o = out + idx * 3;
-    if (hit) {
-        o[0] = (uint8_t)rintf(255.f * c0); o[1] = (uint8_t)rintf(255.f * c1); o[2] = (uint8_t)rintf(255.f * c2);
-    } else if (frame) {
-        const uint8_t* fr = frame + r * 3;
-        o[0] = fr[0]; o[1] = fr[1]; o[2] = fr[2];
-    } else {
-        o[0] = 0; o[1] = 0; o[2] = 0;
-    }
-    if (color_out) { color_out[idx * 3] = c0; color_out[idx * 3 + 1] = c1; color_out[idx * 3 + 2] = c2; }
-    if (face_out) face_out[idx] = gid;
-    if (depth_out) depth_out[idx] = depth;
+    mesh_store(mesh_resolve(zbuf[idx], x, y, scr, nrm, faces, V, F, m), out + idx * 3, frame ? frame + r * 3 : nullptr, idx, color_out, face_out, depth_out);
 }
 
 // verts [P, V, 3] fp32 (mesh frame, as WHMR.forward returns them); faces [F, 3] int32 with every index in [0, V) (the caller checks); vf_ptr [V + 1],
@@ -263,6 +299,134 @@ extern "C" int whmr_mesh_render(const float* verts, int P, int V, const int32_t*
     WHMR_CHECK_LAUNCH();
     hipLaunchKernelGGL(mesh_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, scr, nrm, faces, (const unsigned long long*)zbuf, frame,
                        out, color_out, face_out, depth_out, NI, V, F, H, W, m);
+    WHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// Draw-list form: any number of mesh instances ("draws") into any number of target images in the same three launches -- the overlays of a whole clip,
+// its per-person images, or the frame | overlay | side view | side view strips of render_image_group.  The host packs two device tables (rows of
+// fixed size, little-endian, no implicit padding: whmr_amd._lib.RENDER_IMAGE_DTYPE / RENDER_DRAW_DTYPE restate them, tests/test_mesh_render_clip_cpu.py
+// holds the two sides together through the static_asserts below).  The arithmetic per vertex, per face and per pixel is the device code above.
+struct whmr_render_image {
+    const uint8_t* frame;                       // background, null = black; row y at frame + y * frame_row_stride
+    uint8_t* out;                               // row y at out + y * out_row_stride: a whole tensor or one panel of a strip
+    int64_t frame_row_stride, out_row_stride;   // bytes
+    int64_t pix_off;                            // this image's first element of the packed per-pixel planes (zbuf, color_out, face_out, depth_out)
+    int32_t H, W;
+    float cx, cy;
+};
+struct whmr_render_draw {
+    int32_t row;                                // row of cam_t, focal and the vertex set
+    int32_t verts_set;                          // 0: verts0, 1: verts1
+    int32_t image;                              // target image; draws of one image share its depth buffer
+    float side_cos, side_sin;
+    int32_t reserved[3];
+};
+static_assert(sizeof(whmr_render_image) == 56, "table layout");
+static_assert(offsetof(whmr_render_image, frame) == 0, "table layout");
+static_assert(offsetof(whmr_render_image, out) == 8, "table layout");
+static_assert(offsetof(whmr_render_image, frame_row_stride) == 16, "table layout");
+static_assert(offsetof(whmr_render_image, out_row_stride) == 24, "table layout");
+static_assert(offsetof(whmr_render_image, pix_off) == 32, "table layout");
+static_assert(offsetof(whmr_render_image, H) == 40, "table layout");
+static_assert(offsetof(whmr_render_image, W) == 44, "table layout");
+static_assert(offsetof(whmr_render_image, cx) == 48, "table layout");
+static_assert(offsetof(whmr_render_image, cy) == 52, "table layout");
+static_assert(sizeof(whmr_render_draw) == 32, "table layout");
+static_assert(offsetof(whmr_render_draw, row) == 0, "table layout");
+static_assert(offsetof(whmr_render_draw, verts_set) == 4, "table layout");
+static_assert(offsetof(whmr_render_draw, image) == 8, "table layout");
+static_assert(offsetof(whmr_render_draw, side_cos) == 12, "table layout");
+static_assert(offsetof(whmr_render_draw, side_sin) == 16, "table layout");
+static_assert(offsetof(whmr_render_draw, reserved) == 20, "table layout");
+
+// The targets of a draw list.  The host checks the tables before it uploads them; a row that is out of range all the same is not drawn (nothing is
+// read or written through it).
+struct mesh_draw_targets {
+    const whmr_render_draw* draws; const whmr_render_image* images;
+    int R, NI, has_verts1; long total;
+    __device__ __forceinline__ bool image_ok(int img) const {
+        if ((unsigned)img >= (unsigned)NI) return false;
+        const whmr_render_image& im = images[img];
+        return im.H > 0 && im.W > 0 && im.pix_off >= 0 && im.pix_off + (long)im.H * im.W <= total;
+    }
+    __device__ __forceinline__ int image(int d) const {
+        const whmr_render_draw& dr = draws[d];
+        const bool ok = (unsigned)dr.row < (unsigned)R && (dr.verts_set == 0 || (dr.verts_set == 1 && has_verts1)) && image_ok(dr.image);
+        return ok ? dr.image : -1;
+    }
+    __device__ __forceinline__ mesh_target target(int img) const { return mesh_target{images[img].H, images[img].W, (long)images[img].pix_off}; }
+};
+
+// Launch 1: z-buffer clear of all images + one thread per (draw, vertex); the centre comes from the draw's image, the angle from the draw.
+__global__ __launch_bounds__(256) void mesh_draw_vertex_kernel(const float* __restrict__ verts0, const float* __restrict__ verts1, const int32_t* __restrict__ faces,
+                                                               const int32_t* __restrict__ vf_ptr, const int32_t* __restrict__ vf_idx,
+                                                               const float* __restrict__ cam_t, const float* __restrict__ focal, float* __restrict__ scr,
+                                                               float* __restrict__ nrm, unsigned long long* __restrict__ zbuf, int D, int V, mesh_draw_targets tg,
+                                                               mesh_cam c) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < tg.total) zbuf[idx] = ~0ull;
+    if (idx >= (long)D * V) return;
+    const int d = (int)(idx / V), v = (int)(idx - (long)d * V);
+    const int img = tg.image(d);
+    if (img < 0) return;
+    const whmr_render_draw& dr = tg.draws[d];
+    c.cx = tg.images[img].cx; c.cy = tg.images[img].cy; c.sc = dr.side_cos; c.ss = dr.side_sin;
+    mesh_vertex((dr.verts_set ? verts1 : verts0) + (size_t)dr.row * V * 3, v, faces, vf_ptr, vf_idx, cam_t + (size_t)dr.row * 3, focal + (size_t)dr.row * 2, c,
+                scr + idx * 3, nrm + idx * 3);
+}
+
+// Launch 2: one lane per (draw, face).
+__global__ __launch_bounds__(256) void mesh_draw_faces_kernel(const float* __restrict__ scr, const int32_t* __restrict__ faces, unsigned long long* __restrict__ zbuf,
+                                                              int D, int V, int F, float znear, mesh_draw_targets tg) {
+    mesh_faces(scr, faces, zbuf, (long)blockIdx.x * 256 + threadIdx.x, (long)D * F, V, F, znear, tg);
+}
+
+// Launch 3: blockIdx.y = image, the x dimension strides over its pixels (it is sized for the mean plane: one step when all images have one size).
+__global__ __launch_bounds__(256) void mesh_draw_resolve_kernel(const float* __restrict__ scr, const float* __restrict__ nrm, const int32_t* __restrict__ faces,
+                                                                const unsigned long long* __restrict__ zbuf, float* __restrict__ color_out,
+                                                                int32_t* __restrict__ face_out, float* __restrict__ depth_out, int V, int F, mesh_draw_targets tg,
+                                                                mesh_shade m) {
+    if (!tg.image_ok((int)blockIdx.y)) return;
+    const whmr_render_image im = tg.images[blockIdx.y];
+    const long plane = (long)im.H * im.W;
+    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < plane; r += (long)gridDim.x * 256) {
+        const int y = (int)(r / im.W), x = (int)(r - (long)y * im.W);
+        const long at = im.pix_off + r;
+        mesh_store(mesh_resolve(zbuf[at], x, y, scr, nrm, faces, V, F, m), im.out + y * im.out_row_stride + (long)x * 3,
+                   im.frame ? im.frame + y * im.frame_row_stride + (long)x * 3 : nullptr, at, color_out, face_out, depth_out);
+    }
+}
+
+// verts0, verts1 (nullable) [R, V, 3]; cam_t [R, 3]; focal [R, 2]; faces, vf_ptr, vf_idx, rot, znear and the shading constants as whmr_mesh_render;
+// draws: DEVICE table of D whmr_render_draw, images: DEVICE table of NI whmr_render_image, total_pixels = the sum of H * W over the images.  Scratch:
+// scr, nrm [D, V, 3] fp32, zbuf [total_pixels] uint64.  Optional packed planes (or null): color_out [total_pixels, 3], face_out [total_pixels] (global
+// face id draw * F + face, -1 = background), depth_out [total_pixels].  The nearest face wins a pixel, ties go to the smaller id = the earlier draw.
+extern "C" int whmr_mesh_render_draws(const float* verts0, const float* verts1, int R, int V, const int32_t* faces, int F, const int32_t* vf_ptr,
+                                      const int32_t* vf_idx, const float* cam_t, const float* focal, const void* draws, int D, const void* images, int NI,
+                                      long total_pixels, const float* rot, float znear, float base_r, float base_g, float base_b, float ambient, float k_d,
+                                      float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, float* color_out, int32_t* face_out, float* depth_out,
+                                      void* stream) {
+    if (R <= 0 || V <= 0 || F <= 0 || D < 0 || NI <= 0 || NI > 65535 || total_pixels <= 0 || (long)D * F > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    mesh_cam c{0.f, 0.f, 1.f, 0.f, rot != nullptr, {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}};
+    if (rot)
+        for (int k = 0; k < 9; ++k) c.r[k] = rot[k];
+    mesh_shade m{base_r, base_g, base_b, ambient, k_d, lx, ly, lz};
+    mesh_draw_targets tg{(const whmr_render_draw*)draws, (const whmr_render_image*)images, R, NI, verts1 != nullptr, total_pixels};
+    const long n0 = (long)D * V > total_pixels ? (long)D * V : total_pixels;
+    hipLaunchKernelGGL(mesh_draw_vertex_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, scr, nrm,
+                       (unsigned long long*)zbuf, D, V, tg, c);
+    WHMR_CHECK_LAUNCH();
+    if (D > 0) {
+        hipLaunchKernelGGL(mesh_draw_faces_kernel, dim3((unsigned)(((long)D * F + 255) / 256)), dim3(256), 0, st, scr, faces, (unsigned long long*)zbuf, D, V, F,
+                           znear, tg);
+        WHMR_CHECK_LAUNCH();
+    }
+    const long mean_plane = (total_pixels + NI - 1) / NI;
+    hipLaunchKernelGGL(mesh_draw_resolve_kernel, dim3((unsigned)((mean_plane + 255) / 256), (unsigned)NI), dim3(256), 0, st, scr, nrm, faces,
+                       (const unsigned long long*)zbuf, color_out, face_out, depth_out, V, F, tg, m);
     WHMR_CHECK_LAUNCH();
     return 0;
 }

@@ -15,6 +15,8 @@ all frames, Pillow's 8-bit bilinear resize bit for bit); the camera model runs a
 
     sm = TrackSmoother(model);  out = infer_clip(model, frames, dets_per_frame, track_ids=ids_per_frame, smoother=sm)
 
+With a ``renderer`` ClipPipeline also returns the clip's overlays, drawn by ONE launch group (``render_clip``: whmr_mesh_render_draws).
+
 With a tracker's ids the rows of one person are linked over the frames (and over successive clips) and smoothed by a one-euro filter on the device
 (``whmr_track_smooth``: one launch), and the vertices are recomputed from the smoothed pose and shape: what --smooth of demo/whmr_demo.py:135-144 asks for.
 """
@@ -117,6 +119,18 @@ def render_frame(out, frame_u8, renderer, per_person=False):
     if isinstance(frame_u8, np.ndarray):
         frame_u8 = torch.from_numpy(np.ascontiguousarray(frame_u8)).cuda()
     return renderer.render(frame_u8, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], per_person=per_person)
+
+
+@torch.no_grad()
+def render_clip(out, frames, renderer, frame_index, per_person=False):
+    """``render_frame`` for a whole clip in one launch group (MeshRenderer.render_clip): the rows of the vis_dict ``out`` drawn over their frames.
+    frames: [F, H, W, 3] or a list of frames (device tensors; numpy is uploaded); frame_index: the frame of every row as HOST integers.  Returns a
+    list of F uint8 images, each equal to ``render_frame`` on that frame's rows (a frame without rows: its own bytes), or P images with per_person."""
+    if isinstance(frames, np.ndarray):
+        frames = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
+    elif not torch.is_tensor(frames):
+        frames = [torch.from_numpy(np.ascontiguousarray(f)).cuda() if isinstance(f, np.ndarray) else f for f in frames]
+    return renderer.render_clip(frames, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], frame_index, per_person=per_person)
 
 
 class FramePipeline:
@@ -251,15 +265,15 @@ def infer_clip(model, frames, dets_per_frame, with_full_image=True, pad_to=None,
 class ClipPipeline:
     """infer_clip with the model call replayed from a HIP graph per (padded person count, number of frames, frame size); the input preparation
     (two launches per clip) stays outside the graph, as in FramePipeline.  person_bucket: the person batch is padded to its next multiple, so clips of
-    similar size share a graph.  With ``renderer`` (utils.renderer_cam.MeshRenderer) the call returns (vis_dict, [F overlay images]): one
-    ``render_frame`` launch group per frame over that frame's rows, behind the replayed graph on the same stream, no host sync; a frame without
-    detections comes back as a copy of itself.  With ``smoother`` (a TrackSmoother) and per-call ``track_ids`` the smoothing stage (one filter launch +
-    two SMPL calls) runs behind the replayed graph on the same stream, outside the graph -- its table changes per clip, like the input preparation --
+    similar size share a graph.  With ``renderer`` (utils.renderer_cam.MeshRenderer) the call returns (vis_dict, [F overlay images]): ONE
+    ``render_clip`` launch group for the whole clip, each image what ``render_frame`` draws over that frame's rows, behind the replayed graph on the
+    same stream, no host sync; a frame without detections comes back as a copy of itself; per_person: [P images], one person each.  With
+    ``smoother`` (a TrackSmoother) and per-call ``track_ids`` the smoothing stage (one filter launch + two SMPL calls) runs behind the replayed graph on the same stream, outside the graph -- its table changes per clip, like the input preparation --
     and the renderer draws the smoothed rows; the padding rows never enter a track."""
 
-    def __init__(self, model, with_full_image=True, person_bucket=8, renderer=None, smoother=None):
+    def __init__(self, model, with_full_image=True, person_bucket=8, renderer=None, smoother=None, per_person=False):
         self.model, self.with_full_image, self.person_bucket, self.renderer, self._graphs = model, with_full_image, person_bucket, renderer, {}
-        self.smoother = smoother
+        self.smoother, self.per_person = smoother, per_person
 
     @torch.no_grad()
     def __call__(self, frames, dets_per_frame, track_ids=None):
@@ -279,13 +293,8 @@ class ClipPipeline:
             out = self.smoother.run(out, plan)
         if self.renderer is None:
             return out
-        images, row = [], 0
-        for frame, dets in zip(kw['frames'], dets_per_frame):
-            n = len(dets)
-            images.append(render_frame({k: out[k][row:row + n] for k in ('local_smpl_vertices', 'pred_cam_t', 'focal_length')}, frame, self.renderer)
-                          if n else frame.clone())
-            row += n
-        return out, images
+        index = np.repeat(np.arange(len(dets_per_frame)), [len(d) for d in dets_per_frame])       # from the detections: the host has them
+        return out, render_clip(out, kw['frames'], self.renderer, index, self.per_person)
 
 
 # ----------------------------------------------------------------------------- temporal smoothing of tracked persons
