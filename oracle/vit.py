@@ -34,6 +34,7 @@ def vit_tokens(sd, x, prefix='', num_heads=12, depth=None, eps=1e-6, taps=None, 
     t = t + pos[:, 1:] + pos[:, :1]
     if taps is not None:
         taps['embed'] = t
+        taps['streams'] = [t]                       # the residual stream after the patch embed and after every residual step
     if depth is None:
         depth = 0
         while (p + 'blocks.%d.norm1.weight' % depth) in sd:
@@ -57,9 +58,13 @@ def vit_tokens(sd, x, prefix='', num_heads=12, depth=None, eps=1e-6, taps=None, 
         a = (q @ k.transpose(-2, -1)).softmax(dim=-1)
         h = (a @ v).transpose(1, 2).reshape(B, N, C)
         t = t + dp(F.linear(h, sd[b + 'attn.proj.weight'], sd[b + 'attn.proj.bias']), i, 0)
+        if taps is not None:
+            taps['streams'].append(t)
         h = F.layer_norm(t, (C,), sd[b + 'norm2.weight'], sd[b + 'norm2.bias'], eps)
         h = F.gelu(F.linear(h, sd[b + 'mlp.fc1.weight'], sd[b + 'mlp.fc1.bias']))
         t = t + dp(F.linear(h, sd[b + 'mlp.fc2.weight'], sd[b + 'mlp.fc2.bias']), i, 1)
+        if taps is not None:
+            taps['streams'].append(t)
         if taps is not None and i == 0:
             taps['block0'] = t
     t = F.layer_norm(t, (C,), sd[p + 'last_norm.weight'], sd[p + 'last_norm.bias'], eps)

@@ -1,4 +1,5 @@
-"""Float64 references of the bf16 ViT training kernels, with error bounds derived from the kernels' own arithmetic.
+"""Float64 references of the bf16 ViT training kernels and of the blocked bf16 inference kernels, with error bounds derived from the kernels' own
+arithmetic.
 
 A plain helper module (not collected by pytest); works on CPU and on device tensors.  Every reference takes the inputs of one library call
 AS THE KERNEL RECEIVED THEM (bf16 or fp32 values) and returns ``(r, m)``:
@@ -209,3 +210,171 @@ def colsum(x, prior=None):
     if prior is not None:
         r, m = r + _d(prior), m + _d(prior).abs()
     return r, m
+
+
+# ------------------------------------------------------------------------------------------- blocked bf16 inference path (csrc/gemm_blk16_impl.h,
+# attention_blk16.hip, vit_ops.hip).  Operands arrive in the blocked layout [rows/32][cols/E][32][E] (E = 8 bf16 / 4 fp32) and are compared
+# row-major; rows >= M of the last 32-row block are not part of any comparison.
+
+EPI_BF16, EPI_BF16_GELU, EPI_F32_RES, EPI_F32_POS = 0, 1, 2, 3
+N_ROUND_GEMM_BLK = 0             # gemm_blk16_impl.h:253-256 / :327-329: fp32 accumulator + bias (+ residual), one rounding at the store (rho_out)
+N_ROUND_GEMM_BLK_GELU = 0        # gemm_blk16_impl.h:255: gelu_fast2 of the fp32 value in registers, rounded once at :256 (rho_out)
+N_ROUND_FOLD_CONSUMER = 0        # gemm_blk16_impl.h:253-254: rstd * acc - rstd * mean * colsum + bias in fp32 fmas on the operand it was GIVEN
+N_ROUND_FOLD_SEMANTIC = 1        # gemm_blk16_impl.h:338: the producer rounds the centred row to bf16 (xhat); carried as 2^-8 rstd |t - s| . |W'|^T
+N_ROUND_ATT_BLK = 1              # attention_blk16.hip:209-210: P -> bf16 for the P.V MFMA; the row sum (:208, :258-265) is of the UNROUNDED
+#                                  exponentials and scales the fp32 result (:276).  The N > 240 fallback does the same: attention.hip:309 / :293-296
+GELU_LIP = 1.13                  # max |gelu'| = 1.1289: an error e of the pre-activation moves the exact GELU by at most 1.13 e
+AMP_MAX = 4.0                    # every fold test asserts the amplification of its own inputs (below) is <= this
+
+
+def unblock(t, rows):
+    """blocked [rows/32][cols/E][32][E] -> row-major [rows, cols]"""
+    nb, nu, _, E = t.shape
+    return t.permute(0, 2, 1, 3).reshape(nb * 32, nu * E)[:rows]
+
+
+def block(t):
+    """row-major [R, C] -> blocked [ceil(R/32)][C/E][32][E], padding rows zero"""
+    E = 8 if t.dtype == torch.bfloat16 else 4
+    t = torch.cat([t, t.new_zeros(-t.shape[0] % 32, t.shape[1])], 0)
+    return t.reshape(t.shape[0] // 32, 32, t.shape[1] // E, E).permute(0, 2, 1, 3).contiguous()
+
+
+def _gelu_of(r, m, alpha=0.0):
+    """the exact GELU of a pre-activation known to (r, m, alpha): gelu_fast2 is within GELU_ABS, and |gelu'| <= GELU_LIP"""
+    return gelu(r), GELU_LIP * m, GELU_LIP * alpha + GELU_ABS
+
+
+def gemm_blk(a, w, M, bias=None, epi=EPI_BF16, res=None, res_rows=0):
+    """whmr_gemm_blk without the LayerNorm fold: a [M/32][K/8][32][8], w [N/32][K/8][32][8] bf16 -> (r, m, alpha) of the M x N result.
+    EPI_BF16: a.w^T + bias;  EPI_BF16_GELU: its GELU (alpha GELU_ABS);  EPI_F32_RES: + the blocked fp32 residual as it was BEFORE the call
+    (the kernel may run in place);  EPI_F32_POS: + res[m % res_rows] of a row-major fp32 table.  n_round 0 for all four."""
+    A, W = unblock(a, M), unblock(w, w.shape[0] * 32)
+    if epi == EPI_F32_RES:
+        r, m = gemm(A, W, bias=bias, residual=unblock(res, M))
+    elif epi == EPI_F32_POS:
+        r, m = gemm(A, W, bias=bias, residual=res.reshape(-1, W.shape[0]), res_row_mod=res_rows)
+    else:
+        r, m = gemm(A, W, bias=bias)
+    if epi == EPI_BF16_GELU:
+        return _gelu_of(r, m)
+    return r, m, 0.0
+
+
+def fold_producer(C, M, shift=None, shift_stats=None, shift_out=None):
+    """The emission of a folding producer (gemm_blk16_impl.h:276-299, 330-371), from the fp32 stream C it STORED (blocked, live) and its shift
+    inputs as it received them ->
+      s:      (r, m) of s_m = shift[m] + sum_t shift_stats[m, t, 0] / N in float64 (None without a shift) -- shift_out is held to it, fp32 bound;
+      s_live: the fp32 shift the kernel applied (shift_out where it wrote one; a lone ``shift`` is applied as it is, :289);
+      xhat:   bf16(fp32(C - s_live)), row-major [M, N]: ONE rounding (:338) of values the kernel computed itself -> compare bit for bit;
+      stats:  (r, m) [M, N/256, 2] of (sum o, sum o^2) over the 256 columns of tile t, o = fp32(C - s_live) (:332-337, :359-369);
+              magnitudes sum |o| and sum o^2, kappa KAPPA (a 256-term fp32 sum in a fixed tree)."""
+    c = unblock(C, M).float()
+    N = c.shape[1]
+    T = N // 256
+    s, s_live = None, torch.zeros(M, dtype=torch.float32, device=c.device)
+    if shift is not None or shift_stats is not None:
+        sr, sm = torch.zeros(M, dtype=torch.float64, device=c.device), torch.zeros(M, dtype=torch.float64, device=c.device)
+        if shift is not None:
+            sr, sm = sr + _d(shift).reshape(-1)[:M], sm + _d(shift).reshape(-1)[:M].abs()
+        if shift_stats is not None:
+            assert shift_out is not None, 'the applied shift is only known from shift_out'
+            part = _d(shift_stats).reshape(-1, T, 2)[:M, :, 0]
+            sr, sm = sr + part.sum(1) / N, sm + part.abs().sum(1) / N
+        s = (sr, sm)
+        s_live = (shift_out if shift_out is not None else shift).detach().float().reshape(-1)[:M]
+    o = c - s_live.view(-1, 1)                                                      # fp32, as :332
+    od = o.double().view(M, T, 256)
+    sq = (od * od).sum(-1)
+    stats = (torch.stack([od.sum(-1), sq], -1), torch.stack([od.abs().sum(-1), sq], -1))
+    return {'s': s, 's_live': s_live, 'xhat': o.to(torch.bfloat16), 'stats': stats}
+
+
+def _row_stats(sx, sxx, K, eps):
+    """mean, rstd and the amplification (E[x^2] + mean^2) / (var + eps) of rows known by their sums.
+
+    The consumer forms var = E2 - mean^2 (E2 = sum sxx / K) in one pass in fp32 (gemm_blk16_impl.h:226-229).  E2 and mean^2 each carry a
+    relative error <= kappa, so |d var| <= kappa (E2 + mean^2); rstd = (var + eps)^-1/2 gives d rstd / rstd = -1/2 d var / (var + eps), i.e.
+    |d rstd| / rstd <= 1/2 kappa (E2 + mean^2) / (var + eps) = 1/2 kappa amp.  Every term of the result but the bias is proportional to rstd,
+    so the allowance of a consumer is kappa (1 + amp / 2) m.  amp is 1 + 2 mean^2 / var: 1 for a centred row, 801 at |mean| = 20 std --
+    which is why the tests ASSERT amp <= AMP_MAX on their inputs instead of letting the bound grow with it."""
+    mean = sx / K
+    e2 = sxx / K
+    var = (e2 - mean * mean).clamp_min(0.0)
+    return mean, (var + eps).rsqrt(), (e2 + mean * mean) / (var + eps)
+
+
+def assert_amplification(amp, what):
+    """the CONDITION of every fold check: the rows' amplification is <= AMP_MAX (so kappa (1 + amp / 2) <= 3 kappa) -> the worst one"""
+    a = amp.max().item()
+    assert a <= AMP_MAX, '%s: amplification %.3g of the row statistics exceeds %g -- these inputs do not meet the fold checks\' condition' % (what, a, AMP_MAX)
+    return a
+
+
+def fold_consumer(a, w, M, stats_in, colsum, bias, eps, epi=EPI_BF16):
+    """A fold consumer (gemm_blk16_impl.h:212-261) from the operands it was given: a = the producer's bf16 copy, w = W' = bf16(gamma o W),
+    stats_in [rows][K/256][2], colsum, bias = c -> (r, m, kappa [M, 1], alpha, amp [M]):
+        mean = sum_t sx / K,  var = max(sum_t sxx / K - mean^2, 0),  rstd = (var + eps)^-1/2
+        r = rstd (a . W'^T) - rstd mean colsum + bias,   m = rstd (|a| . |W'|^T + |mean| |colsum|) + |bias|
+    kappa = KAPPA (1 + amp / 2) per row (``_row_stats``).  EPI_BF16_GELU: the GELU of that."""
+    A, W = unblock(a, M), unblock(w, w.shape[0] * 32)
+    K = A.shape[1]
+    st = _d(stats_in).reshape(-1, K // 256, 2)[:M]
+    mean, rstd, amp = _row_stats(st[..., 0].sum(1), st[..., 1].sum(1), K, eps)
+    lin, mlin = gemm(A, W)
+    cs = _d(colsum).view(1, -1)
+    b = _d(bias).view(1, -1) if bias is not None else torch.zeros_like(cs)
+    mean, rstd = mean.view(-1, 1), rstd.view(-1, 1)
+    r = rstd * lin - rstd * mean * cs + b
+    m = rstd * (mlin + mean.abs() * cs.abs()) + b.abs()
+    kappa = KAPPA * (1.0 + 0.5 * amp).view(-1, 1)
+    if epi == EPI_BF16_GELU:
+        return _gelu_of(r, m) + (kappa, amp)
+    return r, m, 0.0, kappa, amp
+
+
+def fold_colsum(w):
+    """colsum[n] = sum_k W'[n, k] of the ROUNDED operand the MFMAs multiply (only then does the mean term cancel) -> (r, m); a long fp32 sum
+    made on the host side: kappa KAPPA_SUM"""
+    W = _d(unblock(w, w.shape[0] * 32))
+    return W.sum(1), W.abs().sum(1)
+
+
+def fold_semantic(C, s, M, w, bias, eps, epi=EPI_BF16):
+    """What a fold consumer's output MEANS: LN(t) . W^T as rstd ((t - s) - mean) . W'^T + c, in float64 from the fp32 stream t = C the producer
+    left (blocked, live), the shift s it applied, and W', c as the consumer got them; mean and rstd are the TRUE statistics of t - s.
+    -> (r, m, alpha, kappa [M, 1], amp [M]):  m = rstd ((|t - s| + |mean|) . |W'|^T) + |c|;  alpha = 2^-8 rstd |t - s| . |W'|^T, the one bf16
+    rounding of the centred row (N_ROUND_FOLD_SEMANTIC).  A consumer that reads another step's statistics, or a producer whose sums and
+    copy disagree, is correct call by call and fails here."""
+    x = unblock(C, M).double() - s.detach().double().reshape(-1)[:M].view(-1, 1)
+    W = _d(unblock(w, w.shape[0] * 32))
+    K = x.shape[1]
+    mean, rstd, amp = _row_stats(x.sum(1), (x * x).sum(1), K, eps)
+    mean, rstd = mean.view(-1, 1), rstd.view(-1, 1)
+    b = _d(bias).view(1, -1) if bias is not None else 0.0
+    mx = x.abs() @ W.abs().t()
+    r = rstd * ((x - mean) @ W.t()) + b
+    m = rstd * (mx + mean.abs() * W.abs().sum(1).view(1, -1)) + (b.abs() if bias is not None else 0.0)
+    alpha = N_ROUND_FOLD_SEMANTIC * U8 * rstd * mx
+    kappa = KAPPA * (1.0 + 0.5 * amp).view(-1, 1)
+    if epi == EPI_BF16_GELU:
+        return _gelu_of(r, m, alpha) + (kappa, amp)
+    return r, m, alpha, kappa, amp
+
+
+def attention_blk(qkv, B, N, H, scale, chunk=96):
+    """whmr_attention_blk (d = 64): ``attention_fwd`` on the unblocked qkv -> (r, m) of o [B*N, H*64]; n_round N_ROUND_ATT_BLK"""
+    return attention_fwd(unblock(qkv, B * N), B, N, H, 64, scale, chunk)[0]
+
+
+def layernorm_blk(x, rows, gamma, beta, eps):
+    """whmr_layernorm_blk on the blocked fp32 stream -> ((r, m) of the result [rows, C], (r, m) of the row means).  Two-pass statistics in fp32
+    (vit_ops.hip:205-229), n_round 0: the bf16 operand form rounds once at the store (rho_out), out_std and mean_out are fp32."""
+    xr = unblock(x, rows)
+    xd = _d(xr)
+    return layernorm(xr, gamma, beta, eps), (xd.mean(1), xd.abs().mean(1))
+
+
+def patch_im2col_blk(x, P, pad):
+    """whmr_patch_im2col_blk: the exact gather of ``patch_im2col`` in the blocked layout, padding rows zero -> compare bit for bit"""
+    return block(patch_im2col(x, P, pad, torch.bfloat16))

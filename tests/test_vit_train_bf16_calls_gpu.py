@@ -1,9 +1,7 @@
 """Every library call of one bf16 ViT training step (forward + backward), checked against its float64 reference (tests/bf16_reference.py) with
-the bound derived from the kernel's own arithmetic.  A recorder wraps every public function of ``whmr_amd._lib``: each top-level call is
+the bound derived from the kernel's own arithmetic.  A recorder (tests/call_recorder.py) wraps every public function of ``whmr_amd._lib``: each top-level call is
 snapshotted (inputs cloned on the current stream), run, and checked right away; a call with no reference, or with a flag its reference does
 not model, fails the test, and the number of calls of each kind is asserted per configuration."""
-import collections
-import inspect
 import os
 import sys
 
@@ -12,79 +10,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bf16_reference as R  # noqa: E402
+import call_recorder  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-# pure helpers: no kernel of their own (or only reached nested inside a checked call)
-ALLOW = {'lib', 'gemm_tn_ok', 'gemm_tn_group_ok', 'splitk_workspace', 'zero_page', 'train_scratch', 'side_stream'}
-# public classes of _lib: ctypes descriptors, and WeightOperands (its refresh() calls the library directly; the copies are checked after the step)
-CLASSES = {'WhmrGemm', 'WhmrGemmBlk', 'WhmrGemmBlkMx', 'WhmrSmplModel', 'WhmrStageTail', 'WhmrMafWeights', 'WhmrTnItem', 'WeightOperands',
-           'ClockProbe'}
 
-
-def _snap(v):
-    if isinstance(v, torch.Tensor):
-        return v.clone()
-    if isinstance(v, (list, tuple)):
-        return type(v)(_snap(x) for x in v)
-    return v
-
-
-class Recorder:
-    def __init__(self, L):
-        self.L, self.depth, self.counts, self.worst = L, 0, collections.Counter(), {}
-        self.sigs = {}
-
-    def install(self, monkeypatch):
-        L = self.L
-        for name, fn in list(vars(L).items()):
-            if name.startswith('_') or not callable(fn):
-                continue
-            if inspect.isclass(fn):
-                assert name in CLASSES, 'new public class in _lib without a decision in this test: %s' % name
-                continue
-            if not inspect.isfunction(fn) or fn.__module__ != L.__name__:
-                continue
-            self.sigs[name] = inspect.signature(fn)
-            monkeypatch.setattr(L, name, self._wrap(name, fn))
-
-    def _wrap(self, name, fn):
-        def call(*args, **kwargs):
-            if self.depth > 0 or name in ALLOW:
-                self.depth += 1
-                try:
-                    return fn(*args, **kwargs)
-                finally:
-                    self.depth -= 1
-            handler = getattr(self, 'on_' + name, None)
-            assert handler is not None, 'top-level call of _lib.%s has no float64 reference' % name
-            b = self.sigs[name].bind(*args, **kwargs)
-            b.apply_defaults()
-            live = dict(b.arguments)
-            snap = {k: _snap(v) for k, v in live.items()}
-            self.depth += 1
-            try:
-                out = fn(*args, **kwargs)
-            finally:
-                self.depth -= 1
-            self.counts[name] += 1
-            handler(live, snap)
-            return out
-        return call
-
-    def record(self, key, ratio):
-        assert ratio <= 1.0, '%s: error exceeds its derived bound (worst ratio %.3g)' % (key, ratio)
-        self.worst[key] = max(self.worst.get(key, 0.0), ratio)
-
-    @staticmethod
-    def _only(live, allowed, defaults):
-        for k, v in live.items():
-            if k in allowed:
-                continue
-            d = defaults[k].default
-            assert v is d or (v is not None and d is not None and not isinstance(v, torch.Tensor) and v == d), \
-                'flag %s=%r is not modelled by the reference' % (k, v)
-
+class Recorder(call_recorder.Recorder):
     # ------------------------------------------------------------------------------------------------------------- one handler per call
     def on_patch_im2col(self, live, s):
         self._only(live, {'x', 'out', 'patch', 'pad'}, self.sigs['patch_im2col'].parameters)
