@@ -133,6 +133,10 @@ int whmr_gemm_blk(const struct whmr_gemm_blk_desc* p, void* stream);
 int whmr_gemm_blk_tile(const struct whmr_gemm_blk_desc* p, int tile, void* stream);
 /* A/B switch: force a tile for the ViT-B shapes (slot 0 qkv N = 2304, 1 proj, 2 fc1 N = 3072, 3 fc2); 0 = chooser. */
 int whmr_gemm_blk_set_tile(int slot, int tile);
+/* Multi-tile launches of the bf16 epilogues (epi 0 / 1) on more tiles than workgroups: g workgroups walk the tiles blockIdx + k g and fetch the
+ * next tile's first half tiles under the current tile's epilogue stores.  0 = default; g > 0: g workgroups (any value gives the same bits);
+ * g < 0: never (one workgroup per tile, as the fp32 epilogues always run). */
+int whmr_gemm_blk_set_grid(int g);
 /* LayerNorm on the blocked fp32 residual stream -> blocked bf16 GEMM operand (out_std 0) or row-major fp32 [rows, C] (out_std 1: last_norm). */
 int whmr_layernorm_blk(const float* x, const float* gamma, const float* beta, void* y, int rows, int C, float eps, int out_std, void* stream);
 /* The same (out_std 0) + the row means mean_out [ceil(rows/32)*32]: the first LayerNorm of the folded chain (vit.py:125 of block 0) runs explicitly and

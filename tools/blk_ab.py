@@ -1,11 +1,13 @@
 """In-model A/B: blocked-layout ViT path vs the row-major path (ViT-B/16 224^2 batch 64, interleaved), + per-slot blocked tile overrides.
-usage: python tools/blk_ab.py ["slot:tile[,slot:tile]" ...]    (tile in hex, e.g. 0:43 for qkv on the 224-row tile)"""
+usage: python tools/blk_ab.py ["slot:tile[,slot:tile]" ...]    (tile in hex, e.g. 0:43 for qkv on the 224-row tile)
+BLK_AB_GRID=g in the environment: whmr_gemm_blk_set_grid(g) for the whole run (256: every bf16-epilogue tile on the multi-tile launches)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from whmr_amd import _lib as L
 from whmr_amd.models.pose_vit import ViT
 dev = torch.device('cuda:0')
+L.lib().whmr_gemm_blk_set_grid(int(os.environ.get('BLK_AB_GRID', '0')))
 B, res = 64, ((256, 192) if os.environ.get('BLK_AB_RES') == '256x192' else 224)
 def timeit(fn, n=10, w=3):
     for _ in range(w): fn()

@@ -7,7 +7,10 @@ drained, the CU it ran on and its shader-clock count.  Per GEMM shape this print
   per ROUND (first / second tile a CU ran): prologue, main loop (and per 32-deep half tile), epilogue issue, store drain, turnover gap on the CU,
   the critical CU's sum, and the effective shader clock.
 
-    python tools/gemm_stamps.py [--lib tools/lab/libwhmr_hip_stamps.so] [--numerics bf16]
+    python tools/gemm_stamps.py [--lib tools/lab/libwhmr_hip_stamps.so] [--grid G]
+
+In a multi-tile launch (gemm_blk16_impl.h, MT) a workgroup's further tiles stamp "entry" behind the previous tile's drain and "first half tile
+landed" behind the barrier in front of their main loop: "prologue" is then what is left of the fixed cost between two tiles of a workgroup.
 """
 import argparse
 import collections
@@ -26,11 +29,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--lib', default=os.path.join(ROOT, 'tools', 'lab', 'libwhmr_hip_stamps.so'))
     ap.add_argument('--batch', type=int, default=64)
+    ap.add_argument('--grid', type=int, default=0, help='whmr_gemm_blk_set_grid: 0 = default, -1 = one workgroup per tile, g > 0 = g workgroups')
     args = ap.parse_args()
     L.LIB_PATH = os.path.abspath(args.lib)
     lib = L.lib()
     lib.whmr_debug_blk_stamps.argtypes = [ctypes.c_void_p, ctypes.c_long]
     lib.whmr_debug_blk_stamps_used.restype = ctypes.c_long
+    lib.whmr_gemm_blk_set_grid(args.grid)
     from whmr_amd.models.pose_vit import ViT
     dev = torch.device('cuda:0')
     torch.manual_seed(0)

@@ -195,6 +195,7 @@ _SIGS = {
     'whmr_gemm_blk': [C.POINTER(WhmrGemmBlk), _P],
     'whmr_gemm_blk_tile': [C.POINTER(WhmrGemmBlk), _I, _P],
     'whmr_gemm_blk_set_tile': [_I, _I],
+    'whmr_gemm_blk_set_grid': [_I],
     'whmr_layernorm_blk': [_P, _P, _P, _P, _I, _I, _F, _I, _P],
     'whmr_gemm_blk_mx': [C.POINTER(WhmrGemmBlkMx), _P],
     'whmr_quantize_mx': [_P, _I, _P, _P, _I, _I, _P],

@@ -593,16 +593,6 @@ __global__ __launch_bounds__((NQT + att16x3_cfg<NQT>::NL) * 64) void attention_b
     }
 }
 
-static int att16_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus = n;
-    }
-    return cus;
-}
-
 template <int NQT>
 static int att16_launch(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t st) {
     using cfg = att16_cfg<NQT>;
@@ -614,7 +604,7 @@ static int att16_launch(const void* qkv, void* out, int B, int N, int H, float s
         attr_done = true;
     }
     const int items = B * H;
-    const int cus = att16_cus();
+    const int cus = whmr_cu_count();
     const int grid = items < cus ? items : cus;
     hipLaunchKernelGGL(kern, dim3(grid), dim3((NQT + cfg::NL) * 64), cfg::LDS, st, (const bf16_t*)qkv, (bf16_t*)out, items, N, H, scale);
     WHMR_CHECK_LAUNCH();
@@ -651,7 +641,7 @@ static int att16x3_launch(const void* qh, const void* ql, void* oh, void* ol, in
         attr_done = true;
     }
     const int items = B * H;
-    const int cus = att16_cus();
+    const int cus = whmr_cu_count();
     const int grid = items < cus ? items : cus;
     // lab = k + 1 forces k (A/B); by default only a launch that fills the chip is staggered (a few workgroups neither move the clock nor should wait)
     const int stagger = lab ? lab - 1 : ((NQT >= 13 && items >= cus) ? 2 : 0);

@@ -11,6 +11,17 @@ typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 #define WHMR_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
+// compute units of the current device (256 on MI355X), asked once: the grid of the kernels that walk their work items
+static inline int whmr_cu_count() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus = n;
+    }
+    return cus;
+}
+
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 
 // fp32 -> bf16, round-to-nearest-even with NaN preserved: the native __bf16 conversion lowers to the gfx950 hardware

@@ -52,6 +52,16 @@ template <int OFF> __device__ __forceinline__ bf16x8_t blk_lds_read128(uint32_t 
     return v;
 }
 
+// 8 bias floats at addr and the 8 colsum floats 1 KiB behind them, read and waited for in one statement the compiler's waitcnt bookkeeping does not see
+// (without a fold the colsum half was never written: the caller discards it)
+__device__ __forceinline__ void blk_lds_read_bias(uint32_t addr, float4 (&bq)[2], float4 (&cq)[2]) {
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:1024\n\tds_read_b128 %3, %4 offset:1040\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(bq[0]), "=&v"(bq[1]), "=&v"(cq[0]), "=&v"(cq[1]) : "v"(addr) : "memory");
+}
+
+// the same value, opaque to the compiler: what is computed from it is computed where it is used, not in front of the loop around it
+__device__ __forceinline__ int blk_per_tile(int v) { asm volatile("" : "+v"(v)); return v; }
+
 // A tile is (MI0 + MI1) row blocks x 256 columns on 8 waves: wave row 0 owns MI0 row blocks, wave row 1 owns MI1.
 template <int MI0, int MI1>
 struct blk_cfg {

@@ -20,6 +20,10 @@
 // MFMA): on every SIMD one wave feeds the matrix pipe while the other talks to LDS and the texture addresser.  In a lock-step loop all
 // 8 waves issue their DMA at the same time and the matrix pipes idle for the ~1000 clk the L1 needs to take 64 KiB (qkv main loop
 // 48 -> 36-38 us in the lab).
+//
+// Launches: one workgroup per tile in XCD-aware order; the bf16 epilogues (0 / 1) on more tiles than CUs run G = 256 workgroups that walk the
+// tiles blockIdx + k G and start the next tile's fetch under the current tile's epilogue (gemm_blk16_impl.h MT, whmr_gemm_blk_set_grid below:
+// ViT-B 224^2 batch 64 -28 / -35 us per forward in two runs, profiles/blk_multitile_ab.txt).
 #include "gemm_blk16_impl.h"
 // (the 32x32x16 kernel of gemm_blk_impl.h is the split-bf16 kernel and nothing else: gemm_blk_x3.hip.  Its bf16 instantiation -- the A/B partner of
 // round 3, WHMR_BLK_MFMA=32 -- the two-barrier schedule and the W-direct main loop no longer exist: DESIGN 6 keeps their numbers.)
@@ -67,6 +71,16 @@ extern "C" int whmr_gemm_blk_set_tile(int slot, int tile) {
     g_blk_force[slot] = tile;
     return 0;
 }
+
+// Multi-tile launches (gemm_blk16_impl.h, MT).  0: G = the CU count rounded down to a multiple of 8 -- block b + k G then runs on the XCD that
+// ran block b + k G of the one-tile-per-workgroup grid, so every XCD's L2 sees the tiles it saw before;  g > 0: g workgroups (any value computes
+// the same bits; tests walk several tiles per workgroup at small shapes with it);  g < 0: never multi-tile.  Figures: profiles/blk_multitile_ab.txt.
+static int g_blk_grid = 0;
+extern "C" int whmr_gemm_blk_set_grid(int g) {
+    g_blk_grid = g;
+    return 0;
+}
+static int blk16_mt_grid() { return g_blk_grid > 0 ? g_blk_grid : g_blk_grid < 0 ? 0 : (whmr_cu_count() & ~7); }
 
 extern "C" int whmr_gemm_blk(const whmr_gemm_blk_desc* pp, void* stream) {
     const whmr_gemm_blk_desc& p = *pp;
