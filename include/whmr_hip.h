@@ -652,6 +652,16 @@ int whmr_iuv_rasterize(const float* verts, int B, int Vsrc, const int64_t* vmap,
                        const float* cam, float fx, float fy, float px, float py, float focal, int orig_h, int orig_w, int H, int W, float* scr,
                        void* zbuf, float* out, int32_t* face_out, void* stream);
 
+/* Depth target of the training step (cfg.MODEL.PyMAF.DEPTH_SUPV_ON): utils/renderer.py:449-533 (Depth_Renderer.verts2depthimg: pytorch3d MeshRasterizer with
+ * blur_radius = ln(1e4) 1e-7, faces_per_pixel 30; image = 1 / zbuf[..., 0], background 0) as core/trainer.py:456-460 uses it, on the camera of
+ * whmr_iuv_rasterize (renderer.py:463-513).  A face covers a pixel centre that is strictly inside it OR whose squared distance to the nearest edge segment is
+ * below blur_radius in NDC units; its depth there is sum_i b_i z_i of the perspective-correct barycentrics clamped to [0, 1] and renormalised (pytorch3d's
+ * clip_barycentric_coords, on because blur_radius > 0); the nearest face wins, ties go to the smaller face index.  verts [B, V, 3]; faces [F, 3] int32;
+ * cam [B, 3]; scratch scr [B, V, 3] fp32 + zbuf [B, H, W] uint64; out [B, 1, H, W] fp32; face_out [B, H, W] int32 or null.  H == W.  Three launches,
+ * deterministic. */
+int whmr_depth_rasterize(const float* verts, int B, int V, const int32_t* faces, int F, const float* cam, float fx, float fy, float px, float py,
+                         float focal, int orig_h, int orig_w, int H, int W, float* scr, void* zbuf, float* out, int32_t* face_out, void* stream);
+
 /* Dense-correspondence losses of the AUX supervision, fused: core/trainer.py:255-298 (body_uv_losses, has_iuv = None) on the targets
  * utils/iuvmap.py:67-110 (iuv_img2map, uv_rois = None) derives from the rendered IUV image (core/trainer.py:464-482).  y [B*H*W, ld]: the IUV head's
  * channels-last logits (predict_u 25 | predict_v 25 | predict_uv_index 25 | predict_ann_index 15; models/iuv_predictor.py:71-91), bf16 (y_bf16,
@@ -664,6 +674,17 @@ int whmr_iuv_losses(const void* y, int y_bf16, long ld, const float* iuv, long s
  * d(g[0] loss_U + g[1] loss_V + g[2] loss_IndexUV + g[3] loss_segAnn) / dy, g [4] on the device. */
 int whmr_iuv_losses_bwd(const void* y, int y_bf16, long ld, const float* iuv, long sb, long sc, long sh, long sw, int B, int H, int W,
                         float point_weight, const float* g, void* dy, long ldg, void* stream);
+
+/* loss_Depth of core/trainer.py:301-317 (depth_losses, applied at :489-496): weight / B * sum of smooth_l1(pred - gt) over all pixels of the samples
+ * with has_smpl != 0 (has_smpl [B] fp32 on the device, null = all; the reference's boolean index is a host read), exactly 0 when none is valid or
+ * weight <= 0.  pred = column col of y [B*H*W, ld] (bf16 or fp32): the depth head (models/depth_predictor.py) is one more output channel of the head
+ * convolution.  gt [B, 1, H, W] fp32 with element strides sb, sh, sw.  partial: >= ceil(B*H*W/256) floats of scratch.  Deterministic. */
+int whmr_depth_loss(const void* y, int y_bf16, long ld, int col, const float* gt, long sb, long sh, long sw, const float* has_smpl, int B, int H, int W,
+                    float weight, float* partial, float* loss, void* stream);
+/* Backward of the above: writes ONLY column col of dy [B*H*W, ldg] (y's dtype) = g[0] * d loss_Depth / d pred; whmr_iuv_losses_bwd fills the rest of
+ * the same buffer first. */
+int whmr_depth_loss_bwd(const void* y, int y_bf16, long ld, int col, const float* gt, long sb, long sh, long sw, const float* has_smpl, int B, int H, int W,
+                        float weight, const float* g, void* dy, long ldg, void* stream);
 
 /* ---- the training objective on preds_dict['smpl_out'][1..3] (core/trainer.py:498-609; csrc/whmr_loss.hip): three launches, no atomics (repeated calls
  * are bit-identical), no allocation and no host read (graph-capturable: the valid counts of the masked terms are summed on the device).

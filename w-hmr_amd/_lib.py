@@ -282,12 +282,15 @@ _SIGS = {
     'whmr_attention_bwd_f32': [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     'whmr_scale_rows_cast': [_P, _P, _P, _I, _I, _I, _P],
     'whmr_iuv_rasterize': [_P, _I, _I, _P, _I, _P, _I, _P, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    'whmr_depth_rasterize': [_P, _I, _I, _P, _I, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     'whmr_mesh_render': [_P, _I, _I, _P, _I, _P, _P, _P, _P, _F, _F, _P, _F, _F, _F, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
                          _P, _P],
     'whmr_mesh_render_draws': [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
                                _P],
     'whmr_iuv_losses': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     'whmr_iuv_losses_bwd': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _L, _P],
+    'whmr_depth_loss': [_P, _I, _L, _I, _P, _L, _L, _L, _P, _I, _I, _I, _F, _P, _P, _P],
+    'whmr_depth_loss_bwd': [_P, _I, _L, _I, _P, _L, _L, _L, _P, _I, _I, _I, _F, _P, _P, _L, _P],
     'whmr_train_losses_workspace': [C.POINTER(_WhmrLossArgs), C.POINTER(C.c_long)],
     'whmr_train_losses': [C.POINTER(_WhmrLossArgs), _P, _P, _P, _P],
     'whmr_train_losses_bwd': [C.POINTER(_WhmrLossArgs), _P, _P, _P],
@@ -844,6 +847,26 @@ def iuv_rasterize(verts, faces, tex, cam, K, focal, orig_size, out_size, vmap=No
     return (out, fo) if want_faces else out
 
 
+def depth_rasterize(verts, faces, cam, K, focal, orig_size, out_size, want_faces=False):
+    """inverse-depth image [B, 1, H, W] of the meshes ``verts`` [B, V, 3] (see include/whmr_hip.h: whmr_depth_rasterize).  K = (fx, fy, px, py)."""
+    _dev(verts, faces, cam)
+    verts, cam = _f32c(verts.contiguous()), _f32c(cam.contiguous())
+    assert faces.dtype == torch.int32 and faces.is_contiguous() and faces.dim() == 2 and faces.shape[1] == 3
+    B, V = verts.shape[0], verts.shape[1]
+    H, W = out_size
+    assert H == W, 'the blur band is defined in the NDC of a square image'
+    assert verts.dim() == 3 and verts.shape[2] == 3 and tuple(cam.shape) == (B, 3)
+    dev = verts.device
+    scr = torch.empty(B, V, 3, dtype=torch.float32, device=dev)
+    zbuf = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    out = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
+    fo = torch.empty(B, H, W, dtype=torch.int32, device=dev) if want_faces else None
+    _check(lib().whmr_depth_rasterize(verts.data_ptr(), B, V, faces.data_ptr(), faces.shape[0], cam.data_ptr(), K[0], K[1], K[2], K[3], focal,
+                                      orig_size[0], orig_size[1], H, W, scr.data_ptr(), zbuf.data_ptr(), out.data_ptr(), _ptr(fo), _stream()),
+           'whmr_depth_rasterize')
+    return (out, fo) if want_faces else out
+
+
 _mesh_ws = {}
 
 
@@ -991,26 +1014,65 @@ def _iuv_loss_args(y, iuv):
     return (y.data_ptr(), int(y.dtype == torch.bfloat16), ld, iuv.data_ptr()) + tuple(iuv.stride()) + (B, H, W)
 
 
-def iuv_losses(y, iuv, point_weight):
+def iuv_losses(y, iuv, point_weight, out=None):
     """(loss_U, loss_V, loss_IndexUV, loss_segAnn) [4] of core/trainer.py:255-298 from the IUV head's channels-last logits (u 25 | v 25 | index 25 |
-    ann 15) and the rendered ground-truth IUV image (include/whmr_hip.h: whmr_iuv_losses)."""
+    ann 15) and the rendered ground-truth IUV image (include/whmr_hip.h: whmr_iuv_losses).  ``out``: >= 4 contiguous fp32 to write them into."""
     a = _iuv_loss_args(y, iuv)
     P = y.shape[0] * y.shape[1] * y.shape[2]
     partial = torch.empty((P + 127) // 128 * 4, dtype=torch.float32, device=y.device)
-    out = torch.empty(4, dtype=torch.float32, device=y.device)
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=y.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= 4
     _check(lib().whmr_iuv_losses(*a, float(point_weight), partial.data_ptr(), out.data_ptr(), _stream()), 'whmr_iuv_losses')
     return out
 
 
 def iuv_losses_bwd(y, iuv, point_weight, g, ldg):
-    """gradient of sum_k g[k] * loss_k with respect to y -> [B*H*W, ldg] in y's dtype, columns >= 90 zero"""
+    """gradient of sum_k g[k] * loss_k with respect to y -> [B*H*W, ldg] in y's dtype, columns >= 90 zero (``g``: the first four entries are read)"""
     a = _iuv_loss_args(y, iuv)
     _dev(g)
     g = _f32c(g.contiguous())
-    assert g.numel() == 4 and ldg >= 90
+    assert g.numel() >= 4 and ldg >= 90
     P = y.shape[0] * y.shape[1] * y.shape[2]
     dy = torch.empty(P, ldg, dtype=y.dtype, device=y.device)
     _check(lib().whmr_iuv_losses_bwd(*a, float(point_weight), g.data_ptr(), dy.data_ptr(), ldg, _stream()), 'whmr_iuv_losses_bwd')
+    return dy
+
+
+def _depth_loss_args(y, col, gt, has_smpl):
+    """y [B, H, W, C]: pixels are rows of one [B*H*W, ld] matrix (a ConvNHWCFn output view), the depth prediction is channel ``col``; gt [B, 1, H, W]
+    fp32, any strides; has_smpl [B] fp32 or None"""
+    _dev(y, gt, has_smpl)
+    B, H, W, Cc = y.shape
+    ld = y.stride(2)
+    assert 0 <= col < Cc <= ld and y.stride(3) == 1 and y.stride(1) == W * ld and y.stride(0) == H * W * ld and y.dtype in (torch.float32, torch.bfloat16)
+    assert gt.dtype == torch.float32 and tuple(gt.shape) == (B, 1, H, W)
+    if has_smpl is not None:
+        assert has_smpl.dtype == torch.float32 and has_smpl.is_contiguous() and has_smpl.numel() == B
+    return (y.data_ptr(), int(y.dtype == torch.bfloat16), ld, col, gt.data_ptr(), gt.stride(0), gt.stride(2), gt.stride(3), _ptr(has_smpl), B, H, W)
+
+
+def depth_loss(y, col, gt, has_smpl, weight, out=None):
+    """loss_Depth [1] of core/trainer.py:301-317 from channel ``col`` of the channels-last head output (include/whmr_hip.h: whmr_depth_loss).
+    ``out``: one contiguous fp32 element to write it into."""
+    a = _depth_loss_args(y, col, gt, has_smpl)
+    P = y.shape[0] * y.shape[1] * y.shape[2]
+    partial = torch.empty((P + 255) // 256, dtype=torch.float32, device=y.device)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=y.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.numel() == 1
+    _check(lib().whmr_depth_loss(*a, float(weight), partial.data_ptr(), out.data_ptr(), _stream()), 'whmr_depth_loss')
+    return out
+
+
+def depth_loss_bwd(y, col, gt, has_smpl, weight, g, dy):
+    """column ``col`` of ``dy`` [B*H*W, ldg] (y's dtype, contiguous) = g * d loss_Depth / d y[..., col]; no other column is touched.  ``g``: one fp32 element."""
+    a = _depth_loss_args(y, col, gt, has_smpl)
+    _dev(g, dy)
+    P = y.shape[0] * y.shape[1] * y.shape[2]
+    assert g.dtype == torch.float32 and g.numel() == 1
+    assert dy.dim() == 2 and dy.shape[0] == P and dy.shape[1] > col and dy.is_contiguous() and dy.dtype == y.dtype
+    _check(lib().whmr_depth_loss_bwd(*a, float(weight), g.data_ptr(), dy.data_ptr(), dy.shape[1], _stream()), 'whmr_depth_loss_bwd')
     return dy
 
 

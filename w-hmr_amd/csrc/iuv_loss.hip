@@ -226,6 +226,71 @@ __global__ __launch_bounds__(IUV_PX) void iuv_loss_bwd_kernel(iuv_args a) {
         for (int c = threadIdx.x; c < ldw; c += IUV_PX) dy[(p0 + r) * ldw + c] = c < F::WORDS ? s[r][c] : 0u;
 }
 
+// ---- depth term (cfg.MODEL.PyMAF.DEPTH_SUPV_ON; core/trainer.py:301-317, depth_losses): the depth head is ONE more output channel of the head
+// convolution's GEMM, so its prediction is column `col` of the same [P, ld] matrix.  loss_Depth = weight / B * sum over the pixels of the samples with
+// has_smpl != 0 of smooth_l1(y[p, col] - gt[p]); the reference's boolean index (a host read) is the mask read here.  One pixel per thread, block sums in a
+// fixed order, the final launch adds the blocks in a fixed order.
+constexpr int DEPTH_PX = 256;
+struct depth_args {
+    const void* y; long ld; int col;
+    const float* gt; long sb, sh, sw;             // target [B, 1, H, W] with element strides (the vitpose crop is a strided view)
+    const float* has_smpl;                        // [B] or null (all valid)
+    int H, W; long P;
+    float scale;                                  // weight / B, 0 when weight <= 0
+    float* partial;                               // forward: [blocks]
+    const float* g;                               // backward: upstream gradient of loss_Depth (one float)
+    void* dy; long ldg;                           // backward: only column `col` of [P, ldg] is written
+};
+
+template <typename T>
+__device__ __forceinline__ bool depth_diff(const depth_args& a, long p, float& d) {
+    const long hw = (long)a.H * a.W;
+    const long b = p / hw, rem = p - b * hw;
+    const int h = (int)(rem / a.W), w = (int)(rem - (long)h * a.W);
+    if (a.has_smpl && a.has_smpl[b] == 0.0f) return false;
+    d = io<T>::ld((const T*)a.y + p * a.ld + a.col) - a.gt[b * a.sb + h * a.sh + w * a.sw];
+    return true;
+}
+
+template <typename T>
+__global__ __launch_bounds__(DEPTH_PX) void depth_loss_fwd_kernel(depth_args a) {
+    __shared__ float red[DEPTH_PX / 64];
+    const long p = (long)blockIdx.x * DEPTH_PX + threadIdx.x;
+    float v = 0.f, d;
+    if (p < a.P && depth_diff<T>(a, p, d)) v = smooth_l1(d);
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) a.partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void depth_loss_final_kernel(const float* partial, int nblk, float scale, float* loss) {
+    __shared__ float s[256];
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < nblk; b += 256) acc += partial[b];
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = scale > 0.f ? s[0] * scale : 0.f;
+}
+
+template <typename T>
+__global__ __launch_bounds__(DEPTH_PX) void depth_loss_bwd_kernel(depth_args a) {
+    const long p = (long)blockIdx.x * DEPTH_PX + threadIdx.x;
+    if (p >= a.P) return;
+    float d, v = 0.f;
+    if (a.scale > 0.f && depth_diff<T>(a, p, d)) v = __builtin_amdgcn_fmed3f(d, -1.0f, 1.0f) * (a.g[0] * a.scale);
+    io<T>::st((T*)a.dy + p * a.ldg + a.col, v);
+}
+
+int depth_check(const void* y, long ld, int col, const float* gt, int B, int H, int W) {
+    if (!y || !gt || B <= 0 || H <= 0 || W <= 0 || col < 0 || col >= ld) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
 int check(const void* y, int y_bf16, long ld, const float* iuv, int B, int H, int W) {
     if (!y || !iuv || B <= 0 || H <= 0 || W <= 0 || ld < IUV_C) return (int)hipErrorInvalidValue;
     if (y_bf16 && ((ld & 1) || ((uintptr_t)y & 3))) return (int)hipErrorInvalidValue;
@@ -262,6 +327,39 @@ extern "C" int whmr_iuv_losses_bwd(const void* y, int y_bf16, long ld, const flo
     iuv_args a{y, ld, iuv, sb, sc, sh, sw, H, W, P, point_weight / (float)B, 1.0f / (float)P, nullptr, g, dy, ldg};
     if (y_bf16) hipLaunchKernelGGL(iuv_loss_bwd_kernel<bf16_t>, dim3(nblk), dim3(IUV_PX), 0, st, a);
     else hipLaunchKernelGGL(iuv_loss_bwd_kernel<float>, dim3(nblk), dim3(IUV_PX), 0, st, a);
+    WHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+// loss_Depth (core/trainer.py:301-317) from column `col` of the head output y [B*H*W, ld] -> loss[1]; partial: scratch of >= ceil(B*H*W / 256) floats.
+extern "C" int whmr_depth_loss(const void* y, int y_bf16, long ld, int col, const float* gt, long sb, long sh, long sw, const float* has_smpl, int B, int H,
+                               int W, float weight, float* partial, float* loss, void* stream) {
+    if (int e = depth_check(y, ld, col, gt, B, H, W)) return e;
+    if (!partial || !loss) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const long P = (long)B * H * W;
+    const int nblk = (int)((P + DEPTH_PX - 1) / DEPTH_PX);
+    depth_args a{y, ld, col, gt, sb, sh, sw, has_smpl, H, W, P, weight > 0.f ? weight / (float)B : 0.f, partial, nullptr, nullptr, 0};
+    if (y_bf16) hipLaunchKernelGGL(depth_loss_fwd_kernel<bf16_t>, dim3(nblk), dim3(DEPTH_PX), 0, st, a);
+    else hipLaunchKernelGGL(depth_loss_fwd_kernel<float>, dim3(nblk), dim3(DEPTH_PX), 0, st, a);
+    WHMR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(depth_loss_final_kernel, dim3(1), dim3(256), 0, st, partial, nblk, a.scale, loss);
+    WHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+// d(g[0] * loss_Depth) / dy: writes ONLY column `col` of dy [B*H*W, ldg] (y's dtype) -- the other columns belong to whmr_iuv_losses_bwd, which runs first
+// on the same stream into the same buffer.  A masked sample's pixels get 0.
+extern "C" int whmr_depth_loss_bwd(const void* y, int y_bf16, long ld, int col, const float* gt, long sb, long sh, long sw, const float* has_smpl, int B, int H,
+                                   int W, float weight, const float* g, void* dy, long ldg, void* stream) {
+    if (int e = depth_check(y, ld, col, gt, B, H, W)) return e;
+    if (!g || !dy || col >= ldg) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const long P = (long)B * H * W;
+    const int nblk = (int)((P + DEPTH_PX - 1) / DEPTH_PX);
+    depth_args a{y, ld, col, gt, sb, sh, sw, has_smpl, H, W, P, weight > 0.f ? weight / (float)B : 0.f, nullptr, g, dy, ldg};
+    if (y_bf16) hipLaunchKernelGGL(depth_loss_bwd_kernel<bf16_t>, dim3(nblk), dim3(DEPTH_PX), 0, st, a);
+    else hipLaunchKernelGGL(depth_loss_bwd_kernel<float>, dim3(nblk), dim3(DEPTH_PX), 0, st, a);
     WHMR_CHECK_LAUNCH();
     return 0;
 }

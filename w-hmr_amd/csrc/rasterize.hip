@@ -10,6 +10,15 @@
 // the pixels of the orig_size image; with pytorch3d's screen <-> NDC conventions the two sign flips cancel and a vertex lands at
 //   u = W/2 + (W / orig_w) (fx (x + cam_1) / z' + px - orig_w / 2),   v = H/2 + (H / orig_h) (fy (y + cam_2) / z' + py - orig_h / 2),   z' = z + t_z
 // (pixel units of the W x H output).  Three launches: clear, one thread per (image, face), one thread per pixel.
+//
+// Depth target of the training step (cfg.MODEL.PyMAF.DEPTH_SUPV_ON): utils/renderer.py:449-533 (Depth_Renderer.verts2depthimg, driven from
+// core/trainer.py:456-460) = MeshRasterizer(blur_radius = ln(1e4) 1e-7, faces_per_pixel = 30) on the same camera, the image being 1 / zbuf[..., 0].
+// Same three launches and the same z-buffer key; what differs from the IUV image (pytorch3d's naive path restated again, parity unpinned):
+//   * coverage: strictly inside, OR the squared distance of the centre to the nearest of the three edge SEGMENTS, in NDC units (1 px = 2 / W of a
+//     square image), is below blur_radius -- a band of sqrt(blur_radius) W / 2 pixels (0.0614 at 128) outside every edge;
+//   * depth: blur_radius > 0 switches pytorch3d's clip_barycentric_coords on -- the perspective-correct barycentrics (from the UNclipped screen
+//     ones) are clamped to [0, 1] and divided by their sum (floored at 1e-5) before pz = sum_i b_i z_i; pz < 0 is skipped;
+//   * output: 1 / (nearest pz), 0 where no face accepts (the reference's where(1 / zbuf == -1, 0): zbuf is -1 on the background).
 #include "common.h"
 
 struct raster_cam { float fx, fy, px, py, focal; int orig_h, orig_w, H, W; };
@@ -61,14 +70,47 @@ __device__ __forceinline__ bool raster_bary(const raster_tri& t, float px, float
     return pz >= 0.f;
 }
 
+// Depth target: coverage with the blur band, depth from the clipped and renormalised perspective-correct barycentrics (see the head of the file).
+__device__ __forceinline__ float raster_seg_dist2(float ax, float ay, float bx, float by, float px, float py) {
+    const float dx = bx - ax, dy = by - ay;
+    const float l2 = dx * dx + dy * dy;
+    float s = l2 > 0.f ? ((px - ax) * dx + (py - ay) * dy) / l2 : 0.f;
+    s = fminf(fmaxf(s, 0.f), 1.f);
+    const float qx = px - (ax + s * dx), qy = py - (ay + s * dy);
+    return qx * qx + qy * qy;
+}
+__device__ __forceinline__ bool raster_bary_blur(const raster_tri& t, float px, float py, float band2, float& pz) {
+    const float e0 = edge_fn(t.v[3], t.v[4], t.v[6], t.v[7], px, py);
+    const float e1 = edge_fn(t.v[6], t.v[7], t.v[0], t.v[1], px, py);
+    const float e2 = edge_fn(t.v[0], t.v[1], t.v[3], t.v[4], px, py);
+    const bool in = t.area > 0.f ? (e0 > 0.f && e1 > 0.f && e2 > 0.f) : (e0 < 0.f && e1 < 0.f && e2 < 0.f);
+    if (!in) {
+        const float d2 = fminf(raster_seg_dist2(t.v[0], t.v[1], t.v[3], t.v[4], px, py),
+                               fminf(raster_seg_dist2(t.v[3], t.v[4], t.v[6], t.v[7], px, py), raster_seg_dist2(t.v[6], t.v[7], t.v[0], t.v[1], px, py)));
+        if (!(d2 < band2)) return false;
+    }
+    const float q0 = (e0 * t.ra) * t.rz0, q1 = (e1 * t.ra) * t.rz1, q2 = (e2 * t.ra) * t.rz2;
+    const float rden = __builtin_amdgcn_rcpf((q0 + q1) + q2);
+    float b0 = fminf(fmaxf(q0 * rden, 0.f), 1.f), b1 = fminf(fmaxf(q1 * rden, 0.f), 1.f), b2 = fminf(fmaxf(q2 * rden, 0.f), 1.f);
+    const float sum = fmaxf((b0 + b1) + b2, 1e-5f);
+    b0 /= sum; b1 /= sum; b2 /= sum;
+    pz = (b0 * t.v[2] + b1 * t.v[5]) + b2 * t.v[8];
+    return pz >= 0.f;                                                                      // false for NaN too
+}
+
 // One lane per (image, face) finds the face's pixel box; boxes of at most RASTER_SMALL pixels (a real SMPL mesh at 128 x 128: 1-4 pixels per
 // face) are walked by that lane, larger ones by the WHOLE wave, 64 pixels at a time (the face's setup is broadcast with readlane): a mesh with
 // a few large triangles -- or the synthetic benchmark mesh, whose random skinning weights stretch every face over a good part of the image --
 // costs sum(box) / 64 per wave instead of max(box).  Same per-pixel arithmetic on both paths (bit-identical coverage).
 #define RASTER_SMALL 16
-__device__ __forceinline__ void raster_pixel(const raster_tri& t, int x, int y, int f, unsigned long long* __restrict__ zrow0, int W) {
+template <bool BLUR>
+__device__ __forceinline__ void raster_pixel(const raster_tri& t, int x, int y, int f, unsigned long long* __restrict__ zrow0, int W, float band2) {
     float b0, b1, b2, pz;
-    if (!raster_bary(t, x + 0.5f, y + 0.5f, b0, b1, b2, pz)) return;
+    if constexpr (BLUR) {
+        if (!raster_bary_blur(t, x + 0.5f, y + 0.5f, band2, pz)) return;
+    } else {
+        if (!raster_bary(t, x + 0.5f, y + 0.5f, b0, b1, b2, pz)) return;
+    }
     const unsigned long long key = ((unsigned long long)__float_as_uint(pz) << 32) | (unsigned)f;
     // the z-buffer only ever decreases: a plain (L2-scope) look first drops the faces that are already hidden -- with n faces over a pixel in
     // random depth order ~ln(n) of them still need the atomic
@@ -76,8 +118,10 @@ __device__ __forceinline__ void raster_pixel(const raster_tri& t, int x, int y, 
     if (__hip_atomic_load(z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(z, key);
 }
 
+// BLUR (the depth target): the pixel box grows by the band (``band`` pixels, ``band2`` = its square) and the per-pixel test is raster_bary_blur
+template <bool BLUR>
 __global__ __launch_bounds__(256) void raster_faces_kernel(const float* __restrict__ scr, const int32_t* __restrict__ faces, unsigned long long* __restrict__ zbuf,
-                                                           int B, int V, int F, int H, int W) {
+                                                           int B, int V, int F, int H, int W, float band, float band2) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const float eps = 1e-8f * 0.25f * H * W;
@@ -93,8 +137,10 @@ __global__ __launch_bounds__(256) void raster_faces_kernel(const float* __restri
         }
         const float xmin = fminf(t.v[0], fminf(t.v[3], t.v[6])), xmax = fmaxf(t.v[0], fmaxf(t.v[3], t.v[6]));
         const float ymin = fminf(t.v[1], fminf(t.v[4], t.v[7])), ymax = fmaxf(t.v[1], fmaxf(t.v[4], t.v[7]));
-        if (xmax >= 0.f && ymax >= 0.f && xmin <= (float)W && ymin <= (float)H) {                  // also drops NaN vertices
-            x0 = (int)floorf(xmin - 0.5f); x1 = (int)ceilf(xmax - 0.5f); y0 = (int)floorf(ymin - 0.5f); y1 = (int)ceilf(ymax - 0.5f);
+        const float grow = BLUR ? band : 0.f;
+        if (xmax + grow >= 0.f && ymax + grow >= 0.f && xmin - grow <= (float)W && ymin - grow <= (float)H) {        // also drops NaN vertices
+            x0 = (int)floorf(xmin - grow - 0.5f); x1 = (int)ceilf(xmax + grow - 0.5f);
+            y0 = (int)floorf(ymin - grow - 0.5f); y1 = (int)ceilf(ymax + grow - 0.5f);
             x0 = x0 < 0 ? 0 : x0; y0 = y0 < 0 ? 0 : y0; x1 = x1 > W - 1 ? W - 1 : x1; y1 = y1 > H - 1 ? H - 1 : y1;
         }
     } else {
@@ -107,7 +153,7 @@ __global__ __launch_bounds__(256) void raster_faces_kernel(const float* __restri
     if (npx > 0 && npx <= RASTER_SMALL) {
         unsigned long long* z0 = zbuf + (size_t)b * H * W;
         for (int y = y0; y <= y1; ++y)
-            for (int x = x0; x <= x1; ++x) raster_pixel(t, x, y, f, z0, W);
+            for (int x = x0; x <= x1; ++x) raster_pixel<BLUR>(t, x, y, f, z0, W, band2);
     }
     unsigned long long big = __ballot(npx > RASTER_SMALL);
     while (big) {
@@ -129,7 +175,7 @@ __global__ __launch_bounds__(256) void raster_faces_kernel(const float* __restri
         for (int ty = uy0; ty <= uy1; ty += th)
             for (int tx = ux0; tx <= ux1; tx += tw) {
                 const int x = tx + lx, y = ty + ly;
-                if (x <= ux1 && y <= uy1) raster_pixel(u, x, y, uf, z0, W);
+                if (x <= ux1 && y <= uy1) raster_pixel<BLUR>(u, x, y, uf, z0, W, band2);
             }
     }
 }
@@ -177,10 +223,46 @@ extern "C" int whmr_iuv_rasterize(const float* verts, int B, int Vsrc, const int
     const long n0 = (long)B * V > (long)B * H * W ? (long)B * V : (long)B * H * W;
     hipLaunchKernelGGL(raster_project_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, verts, vmap, cam, scr, (unsigned long long*)zbuf, B, V, Vsrc, c);
     WHMR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(raster_faces_kernel, dim3((unsigned)(((long)B * F + 255) / 256)), dim3(256), 0, st, scr, faces, (unsigned long long*)zbuf, B, V, F, H, W);
+    hipLaunchKernelGGL(raster_faces_kernel<false>, dim3((unsigned)(((long)B * F + 255) / 256)), dim3(256), 0, st, scr, faces, (unsigned long long*)zbuf, B, V, F,
+                       H, W, 0.f, 0.f);
     WHMR_CHECK_LAUNCH();
     hipLaunchKernelGGL(raster_resolve_kernel, dim3((unsigned)(((long)B * H * W + 255) / 256)), dim3(256), 0, st, scr, faces, tex,
                        (const unsigned long long*)zbuf, out, face_out, B, V, H, W);
+    WHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+// the z-buffer key already holds the nearest accepted pz (its high word): nothing is recomputed
+__global__ __launch_bounds__(256) void depth_resolve_kernel(const unsigned long long* __restrict__ zbuf, float* __restrict__ out, int32_t* __restrict__ face_out,
+                                                            long npix) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= npix) return;
+    const unsigned long long key = zbuf[idx];
+    const bool hit = key != ~0ull;
+    out[idx] = hit ? 1.0f / __uint_as_float((unsigned)(key >> 32)) : 0.f;
+    if (face_out) face_out[idx] = hit ? (int)(key & 0xffffffffu) : -1;
+}
+
+// Inverse-depth image of the meshes (see the head of the file): verts [B, V, 3] fp32 (no vertex duplication, no texture); faces [F, 3] int32;
+// cam [B, 3]; scratch as whmr_iuv_rasterize; out [B, 1, H, W]; face_out [B, H, W] int32 or null.  H == W (pytorch3d scales the NDC of a
+// non-square image differently; the reference's DP_HEATMAP_SIZE is square).
+extern "C" int whmr_depth_rasterize(const float* verts, int B, int V, const int32_t* faces, int F, const float* cam, float fx, float fy, float px, float py,
+                                    float focal, int orig_h, int orig_w, int H, int W, float* scr, void* zbuf, float* out, int32_t* face_out, void* stream) {
+    if (B <= 0 || V <= 0 || F <= 0 || H <= 0 || W != H || orig_h <= 0 || orig_w <= 0) return (int)hipErrorInvalidValue;
+    if (!verts || !faces || !cam || !scr || !zbuf || !out) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    raster_cam c{fx, fy, px, py, focal, orig_h, orig_w, H, W};
+    const double blur = 9.210340371976182e-7;                                              // ln(1 / 1e-4) * 1e-7, renderer.py:494
+    const float band2 = (float)(blur * 0.25 * (double)W * (double)W), band = sqrtf(band2);
+    const long npix = (long)B * H * W;
+    const long n0 = (long)B * V > npix ? (long)B * V : npix;
+    hipLaunchKernelGGL(raster_project_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, verts, (const int64_t*)nullptr, cam, scr,
+                       (unsigned long long*)zbuf, B, V, V, c);
+    WHMR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(raster_faces_kernel<true>, dim3((unsigned)(((long)B * F + 255) / 256)), dim3(256), 0, st, scr, faces, (unsigned long long*)zbuf, B, V, F,
+                       H, W, band, band2);
+    WHMR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(depth_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)zbuf, out, face_out, npix);
     WHMR_CHECK_LAUNCH();
     return 0;
 }

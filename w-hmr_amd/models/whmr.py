@@ -320,6 +320,17 @@ class IUV_predict_layer(nn.Module):
         self.predict_uv_index = nn.Conv2d(feat_dim, 25, final_cov_k, 1, pad)
 
 
+class Depth_predict_layer(nn.Module):
+    """Parameter container of models/depth_predictor.py:12-28 (dpth_head, whmr.py:400-401 under cfg.MODEL.PyMAF.DEPTH_SUPV_ON): one 3x3 convolution
+    to a single channel, torch's default Conv2d initialisation as in the reference.  The training forward runs it as one more output channel of the
+    IUV head's GEMM (train/whmr_train.py::dp_head_train).  The reference also evaluates it in eval mode and discards the result (whmr.py:660-678); no
+    inference view here runs it -- the same deliberate difference as ``dp_out: []`` in eval."""
+
+    def __init__(self, feat_dim=256, final_cov_k=3):
+        super().__init__()
+        self.predict_depth = nn.Conv2d(feat_dim, 1, final_cov_k, 1, 1 if final_cov_k == 3 else 0)
+
+
 class WHMR(nn.Module):
     """whmr.py:308-678 (vitpose branch)."""
 
@@ -349,6 +360,8 @@ class WHMR(nn.Module):
         self.transformer = nn.ModuleList()                                            # dead in the reference (whmr.py:362-394)
         if cfg.MODEL.PyMAF.AUX_SUPV_ON:
             self.dp_head = IUV_predict_layer(feat_dim=256)
+        if cfg.MODEL.PyMAF.DEPTH_SUPV_ON:                                             # whmr.py:400-401
+            self.dpth_head = Depth_predict_layer(feat_dim=256)
         self.conv = nn.Sequential(nn.Conv2d(256, 64, 7, 3, 0, bias=False), nn.Conv2d(64, 5, 7, 2, 0, bias=False))
         td = _Holder()                                                                # timm Block(dim=216, heads=2) names
         _ln_params(td, 'norm1', 216)

@@ -4,7 +4,8 @@ Reference: core/trainer.py:413-464 (targets) and :466-609 (loss_dict).  The refe
 masks (``x[has_smpl]``, :221-223, :235-236, :243-246) and branch on ``len(...) > 0`` -- each a host synchronisation, so that code cannot be part
 of a captured step -- and evaluate 15-24 scalar terms as a few tiny launches each.  ``WHMRLossFn`` is ONE autograd node over the three supervised
 stages: csrc/whmr_loss.hip sums every term in two launches (fixed order, no atomics), counts the valid samples on the device and writes all
-gradients in a third.  The dense-correspondence terms stay with ``IUVLossFn`` (train/aux_supervision.py).
+gradients in a third.  The dense-correspondence terms stay with ``IUVLossFn`` (train/aux_supervision.py); with cfg.MODEL.PyMAF.DEPTH_SUPV_ON they and
+``loss_Depth`` (:301-317, :489-496) come from ``AuxLossFn``, one node over the 91-channel head output.
 """
 import torch
 
@@ -12,7 +13,8 @@ from .. import _lib as L
 from ..core.cfgs import cfg
 from ..core.constants import FOCAL_LENGTH
 from ..utils.geometry import estimate_translation
-from .aux_supervision import IUVLossFn, body_uv_losses, gt_camera_from_translation, render_iuv_targets
+from .aux_supervision import (AuxLossFn, IUVLossFn, body_uv_losses, depth_losses, fused_aux_operand, gt_camera_from_translation, render_depth_target,
+                              render_iuv_targets)
 from .heads_autograd import downsample_csr
 from ..utils.iuvmap import iuv_img2map
 
@@ -21,6 +23,7 @@ TERM_KEYS = ('loss_regr_pose', 'loss_regr_betas', 'loss_keypoints_3d', 'loss_sha
              'loss_keypoints', 'loss_keypoints_world', 'loss_focal_length')
 DICT_ORDER = (0, 1, 7, 8, 9, 2, 3, 4, 5, 6)
 IUV_KEYS = ('loss_U', 'loss_V', 'loss_IndexUV', 'loss_segAnn')
+DEPTH_KEY = 'loss_Depth'
 
 
 def _f32(t):
@@ -110,8 +113,13 @@ def _iuv_terms(d, iuv_image_gt):
 
 def compute_losses(preds_dict, targets, options=None):
     """core/trainer.py:466-591: ``loss_dict`` with the reference's keys (``loss_regr_pose_1`` ... ``loss_cam_3``; with cfg.MODEL.PyMAF.AUX_SUPV_ON
-    and ``targets['iuv_image_gt']`` also ``loss_U-1`` ... ``loss_segAnn-1``, has_iuv = None as in ``aux_supervision_loss``).  ``targets``: the batch
-    dictionary with the entries of ``build_targets``; ``options``: anything with ``openpose_train_weight`` / ``gt_train_weight`` (defaults 0. / 1.)."""
+    and ``targets['iuv_image_gt']`` also ``loss_U-1`` ... ``loss_segAnn-1``, has_iuv = None as in ``aux_supervision_loss``; with
+    cfg.MODEL.PyMAF.DEPTH_SUPV_ON, a ``dpth_out`` entry and ``targets['depth_image_gt']`` also ``loss_Depth-1``, :489-496, masked by
+    ``targets['has_smpl']``).  ``targets``: the batch dictionary with the entries of ``build_targets``; ``options``: anything with
+    ``openpose_train_weight`` / ``gt_train_weight`` (defaults 0. / 1.)."""
+    if cfg.MODEL.PyMAF.DEPTH_SUPV_ON and not cfg.MODEL.PyMAF.AUX_SUPV_ON:
+        # the reference creates its depth renderer, and renders the target, only under AUX_SUPV_ON (core/trainer.py:167-171, :442-460)
+        raise ValueError('cfg.MODEL.PyMAF.DEPTH_SUPV_ON needs cfg.MODEL.PyMAF.AUX_SUPV_ON: the depth target is rendered with the IUV target')
     smpl_out = preds_dict['smpl_out']
     assert len(smpl_out) == L.LOSS_STAGES + 1, 'three supervised stages behind the mean-pose entry (core/trainer.py:508-513)'
     kp_2d, focal, verts = float(cfg.LOSS.KP_2D_W) > 0, bool(cfg.MODEL.PyMAF.FOCAL_SUPV_ON), float(cfg.LOSS.VERT_W) > 0
@@ -132,12 +140,28 @@ def compute_losses(preds_dict, targets, options=None):
     vectors = []
     iuv = targets.get('iuv_image_gt')
     dp_out = preds_dict.get('dp_out') or []
+    depth = targets.get('depth_image_gt')
+    dpth_out = (preds_dict.get('dpth_out') or []) if (cfg.MODEL.PyMAF.DEPTH_SUPV_ON and depth is not None) else []
+    w_point = float(cfg.LOSS.POINT_REGRESSION_WEIGHTS)
+    fused = {}                                              # index into dpth_out -> its term, where AuxLossFn covered both heads' entries
     if cfg.MODEL.PyMAF.AUX_SUPV_ON and iuv is not None:                                                        # trainer.py:469-487
         for i, d in enumerate(dp_out):
-            v = _iuv_terms(d, iuv)
+            y = fused_aux_operand(d, dpth_out[i], iuv, depth) if i < len(dpth_out) else None
+            if y is not None:
+                v = AuxLossFn.apply(y, iuv, depth, targets.get('has_smpl'), w_point)
+                fused[i] = v[4]
+            else:
+                v = _iuv_terms(d, iuv)
             vectors.append(v)
             for j, k in enumerate(IUV_KEYS):
                 out['%s%d' % (k, i - len(dp_out))] = v[j]
+    for i, d in enumerate(dpth_out):                                                                           # trainer.py:489-496
+        if i in fused:
+            out['%s%d' % (DEPTH_KEY, i - len(dp_out))] = fused[i]
+        else:
+            v = depth_losses(d, depth, targets.get('has_smpl')).reshape(1)
+            vectors.append(v)
+            out['%s%d' % (DEPTH_KEY, i - len(dp_out))] = v[0]
     for s, ks in enumerate(live):
         for k in ks:
             out['%s_%d' % (TERM_KEYS[k], s + 1)] = losses[s * L.LOSS_TERMS + k]
@@ -159,11 +183,12 @@ def total_loss(loss_dict):
 
 
 @torch.no_grad()
-def build_targets(model, input_batch, iuv_maker=None, img_res=224):
+def build_targets(model, input_batch, iuv_maker=None, img_res=224, depth_maker=None):
     """core/trainer.py:413-464 with kernels the forward already uses: SMPL of the ground-truth parameters (:415-425), the two mesh down-samplings
     (:422-423), the camera translation fitted to the 2-D keypoints (:429-436; ``img_res`` = options.img_res) and -- with ``iuv_maker`` -- the
-    rendered dense-correspondence image (:442-462, valid_fit = all).  -> the batch's loss inputs as fp32 device tensors plus ``opt_vertices``,
-    ``opt_sub_vertices``, ``opt_temp_vertices``, ``opt_joints``, ``opt_cam_t`` (and ``iuv_image_gt``)."""
+    rendered dense-correspondence image (:442-462, valid_fit = all) and -- with ``depth_maker`` (a ``utils.renderer.Depth_Renderer``) -- the
+    inverse-depth image of the same mesh and camera (:456-460).  -> the batch's loss inputs as fp32 device tensors plus ``opt_vertices``,
+    ``opt_sub_vertices``, ``opt_temp_vertices``, ``opt_joints``, ``opt_cam_t`` (and ``iuv_image_gt``, ``depth_image_gt``)."""
     keys = ('pose', 'betas', 'pose_3d', 'has_smpl', 'has_pose_3d', 'keypoints', 'keypoints_world', 'orig_shape', 'bbox_width', 'bbox_height', 'focal')
     for k in keys:
         if k in input_batch and not input_batch[k].is_cuda:
@@ -180,7 +205,11 @@ def build_targets(model, input_batch, iuv_maker=None, img_res=224):
     kp = t['keypoints'].clone()
     kp[:, :, :-1] = 0.5 * img_res * (kp[:, :, :-1] + 1)                                 # trainer.py:430-431
     t['opt_cam_t'] = estimate_translation(out.joints, kp, focal_length=FOCAL_LENGTH, img_size=[cfg.IMG_RES.WIDTH, cfg.IMG_RES.HEIGHT])
-    if iuv_maker is not None:
+    if iuv_maker is not None or depth_maker is not None:
         cam = gt_camera_from_translation(t['opt_cam_t'], focal_length=FOCAL_LENGTH)
-        t['iuv_image_gt'], _ = render_iuv_targets(iuv_maker, out.vertices, cam, vitpose_crop=cfg.MODEL.PyMAF.BACKBONE == 'vitpose', maps=False)
+        crop = cfg.MODEL.PyMAF.BACKBONE == 'vitpose'
+        if iuv_maker is not None:
+            t['iuv_image_gt'], _ = render_iuv_targets(iuv_maker, out.vertices, cam, vitpose_crop=crop, maps=False)
+        if depth_maker is not None:
+            t['depth_image_gt'] = render_depth_target(depth_maker, out.vertices, cam, vitpose_crop=crop)
     return t

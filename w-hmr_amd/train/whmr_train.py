@@ -33,7 +33,7 @@ from .. import _lib as L
 from ..core.cfgs import cfg
 from ..core.constants import FOCAL_LENGTH
 from ..parallel.sync_bn import batch_norm_1d
-from .aux_supervision import IUVHeadOutput
+from .aux_supervision import DepthHeadOutput, IUVHeadOutput
 from .deconv_autograd import DeconvBNReLUFn
 from .heads_autograd import TzComposedFn, AttentionF32Fn, ConvNHWCFn, DownsampleFn, GeluFn, LayerNormFn, LinearFn, MatToAAFn, RegressorPostFn
 from .maf_autograd import MAFSampleFn, MapForkFn
@@ -159,17 +159,29 @@ def _tz_tail(model, t, B):
     return 10.0 * torch.sigmoid(y).squeeze(-1)
 
 
-def dp_head_train(model, f_nhwc, passthrough=False):
+def dp_head_train(model, f_nhwc, passthrough=False, iuv=True, depth=False):
     """IUV_predict_layer.forward (models/iuv_predictor.py:71-91, called at whmr.py:656-658 when AUX_SUPV_ON): four 3x3 convolutions of the last
     feature map, run as ONE implicit GEMM over the concatenated output channels (25 + 25 + 25 + 15); NCHW views of the NHWC result.
-    ``passthrough``: -> (outputs, f_nhwc handed on by the convolution's node, see ConvNHWCFn)."""
-    h = model.dp_head
-    convs = (h.predict_u, h.predict_v, h.predict_uv_index, h.predict_ann_index)
+    ``passthrough``: -> (outputs, f_nhwc handed on by the convolution's node, see ConvNHWCFn).
+    ``depth``: Depth_predict_layer.forward (models/depth_predictor.py:24-28, whmr.py:660-662 when DEPTH_SUPV_ON) is the same 3x3 / stride 1 / padding 1
+    convolution of the same map: its weight and bias are concatenated behind the IUV head's (channel 90 of 91; the bf16 GEMM is padded to 128 columns
+    either way) -- no launch of its own, forward or backward.  ``outputs`` is then the pair (dp_out entry, dpth_out entry); ``iuv=False`` runs the depth
+    head alone through the same node (dp_out entry None)."""
+    convs = []
+    if iuv:
+        h = model.dp_head
+        convs += [h.predict_u, h.predict_v, h.predict_uv_index, h.predict_ann_index]
+    if depth:
+        convs.append(model.dpth_head.predict_depth)
     w = torch.cat([c.weight for c in convs], 0)
     b = torch.cat([c.bias for c in convs], 0)
     y = ConvNHWCFn.apply(f_nhwc, w, 1, model._dt, convs[0].padding[0], b, passthrough)
     y, f_next = y if passthrough else (y, None)
-    out = IUVHeadOutput(y, [c.out_channels for c in convs])                            # the four NCHW fp32 views appear on first access
+    if depth:
+        n = y.shape[-1] - 1
+        out = (IUVHeadOutput(y[..., :n], [c.out_channels for c in convs[:4]], full=y) if iuv else None, DepthHeadOutput(y, n))
+    else:
+        out = IUVHeadOutput(y, [c.out_channels for c in convs])                        # the four NCHW fp32 views appear on first access
     return (out, f_next) if passthrough else out
 
 
@@ -241,6 +253,7 @@ def whmr_forward_train(model, x, center, scale, bbox_height, orig_shape, bbox_in
     s_feat = model.feature_extractor(x)                                               # [B,768,Hp,Wp] view of NHWC tokens, ViTFn node
     f = s_feat.permute(0, 2, 3, 1).contiguous().to(dt)
     aux = bool(cfg.MODEL.PyMAF.AUX_SUPV_ON and hasattr(model, 'dp_head'))
+    dpth = bool(cfg.MODEL.PyMAF.DEPTH_SUPV_ON and hasattr(model, 'dpth_head'))          # whmr.py:660-662
     tz_grad = int(cfg.TRAIN.STAGE) != 1                                               # stage 1 trains the Tz head on a detached map
 
     # Every feature map has two or three consumers (the next deconv stage or the two heads, and the stage's sampler).  A map is handed
@@ -259,14 +272,14 @@ def whmr_forward_train(model, x, center, scale, bbox_height, orig_shape, bbox_in
             return tz_head_train(model, fm.detach(), tail_stream=tail), fm
         return tz_head_train(model, fm, True, tail_stream=tail)
 
-    def dp_head(fm):                                                                   # whmr.py:656-658
-        return dp_head_train(model, fm, True)
+    def dp_head(fm):                                                                   # whmr.py:656-662
+        return dp_head_train(model, fm, True, iuv=aux, depth=dpth)
 
     # Stage i of the regressor loop only reads feature map i, and the Tz head only enters the stages' projections (whmr.py:142-173), not the
     # next stage's input: after the first deconv stage the HEAVY chain (deconv 2, deconv 3, Tz head, IUV head: a few large launches) runs on a
     # side stream and the loop (hundreds of small launches) beside it on the main one; the Tz-dependent projections of the three stages follow
     # the join.  autograd runs every node's backward on the stream of its forward, so the backward pass overlaps the same way.
-    fmaps, dp_out, map_ready = [deconv(0, f, chain=False)[0]], [], [None, None, None]
+    fmaps, dp_out, dpth_out, map_ready = [deconv(0, f, chain=False)[0]], [], [], [None, None, None]
     f_first = fmaps[0]
     heavy = tail = None
     if OVERLAP_HEAVY:
@@ -298,11 +311,14 @@ def whmr_forward_train(model, x, center, scale, bbox_height, orig_shape, bbox_in
         if heavy is not None:
             tz_ready = torch.cuda.Event()
             tz_ready.record(tail if tail is not None else heavy)
-        if aux:
+        if aux and not dpth:
             d, _ = dp_head(fm_heads)
             dp_out = [d]
+        elif dpth:                                                                     # the depth head rides in the IUV head's GEMM (or runs alone)
+            (d, dd), _ = dp_head(fm_heads)
+            dp_out, dpth_out = [d] if d is not None else [], [dd]
     if heavy is not None and HEAVY_FIRST and not capturing:
-        _backward_first([Tz, fmaps[1], fmaps[2]] + [d.nhwc for d in dp_out], [f_first])
+        _backward_first([Tz, fmaps[1], fmaps[2]] + [d.nhwc for d in dp_out + dpth_out], [f_first])
     for i in range(3):
         model.maf_extractor[i].im_feat = fmaps[i].detach().permute(0, 3, 1, 2)
 
@@ -350,7 +366,7 @@ def whmr_forward_train(model, x, center, scale, bbox_height, orig_shape, bbox_in
     if heavy is not None:                                                              # join
         main.wait_stream(heavy)
         if not torch.cuda.is_current_stream_capturing():
-            for d in dp_out:
+            for d in dp_out + dpth_out:
                 d.nhwc.record_stream(main)
     vis_feat = [s_feat.detach()] + [m.detach().permute(0, 3, 1, 2) for m in fmaps]
-    return {'smpl_out': outs, 'dp_out': dp_out, 'dpth_out': [], 'global_output': g_out}, vis_feat
+    return {'smpl_out': outs, 'dp_out': dp_out, 'dpth_out': dpth_out, 'global_output': g_out}, vis_feat
