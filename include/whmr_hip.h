@@ -775,6 +775,26 @@ int whmr_mesh_render_draws(const float* verts0, const float* verts1, int R, int 
                            long total_pixels, const float* rot, float znear, float base_r, float base_g, float base_b, float ambient, float k_d,
                            float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, float* color_out, int32_t* face_out, float* depth_out,
                            void* stream);
+/* The scene form (same file, same device code): the draw list plus at most ONE checkerboard ground plane per image, the add_ground_plane of
+ * utils/renderer_cam.py:53,95-104 (the plane itself, PARE's get_checkerboard_plane, is third-party: it is defined in the kernel file's header).  A
+ * third DEVICE table, grounds, has one row per image (the layout is asserted in csrc/mesh_render.hip as whmr_ground_row and restated by
+ * whmr_amd._lib.RENDER_GROUND_DTYPE):
+ *   grounds, NI rows of 32 bytes:  0 draw (int32: the draw that owns the plane -- its row of cam_t / focal is the plane's camera, its mesh gives the
+ *     height -- it must target this image and be the image's only draw (the host checks); -1 = no plane)   4 given (int32, 0: y = the lowest
+ *     world-frame point of the owning draw's mesh = -max_v p_y, found on the device, NaN vertices skipped; 1: y as given)   8 y (float, world frame,
+ *     y up)   12 half (float > 0: the square |x|, |z| <= half)   16 n (int32 >= 1, tiles per side)   20 dark   24 light (float, grey of the tiles
+ *     with ix + iz even / odd)   28 reserved
+ * A plane pixel (the ray of the pixel's centre meets the square at a finite depth Z_g > znear, nearer than the winning face if there is one; a tie
+ * goes to the mesh) holds the tile's grey in out / color_out, Z_g in depth_out, -1 in face_out and ix * n + iz in ground_out.  heights [max(D, 1)]
+ * int32: scratch (cleared in launch 1, reduced with an integer atomic max in launch 2, read in launch 3: no host read); ground_out [total_pixels] int32
+ * or null (-1 = no plane there); ground_y [NI] fp32: the height used for every image, NaN = no plane (none asked for, a row out of range, or a mesh
+ * without a finite vertex).  Everything else as whmr_mesh_render_draws, whose bytes a table without planes reproduces.  Three launches, no allocation,
+ * no synchronisation; bit-reproducible. */
+int whmr_mesh_render_scene(const float* verts0, const float* verts1, int R, int V, const int32_t* faces, int F, const int32_t* vf_ptr,
+                           const int32_t* vf_idx, const float* cam_t, const float* focal, const void* draws, int D, const void* images, int NI,
+                           long total_pixels, const void* grounds, const float* rot, float znear, float base_r, float base_g, float base_b,
+                           float ambient, float k_d, float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, int32_t* heights,
+                           float* color_out, int32_t* face_out, float* depth_out, int32_t* ground_out, float* ground_y, void* stream);
 
 /* ---- training input side (csrc/augment.hip): the sample-making of BaseDataset.__getitem__ (datasets/base_dataset.py:249-384) for a whole batch --
  * rgb_processing (:183-207) over utils/imutils.py:crop (:54-88: integer box, skimage rotate, Pillow bicubic resize), Normalize and the

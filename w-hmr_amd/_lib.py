@@ -287,6 +287,8 @@ _SIGS = {
                          _P, _P],
     'whmr_mesh_render_draws': [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
                                _P],
+    'whmr_mesh_render_scene': [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P,
+                               _P, _P, _P, _P, _P],
     'whmr_iuv_losses': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     'whmr_iuv_losses_bwd': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _L, _P],
     'whmr_depth_loss': [_P, _I, _L, _I, _P, _L, _L, _L, _P, _I, _I, _I, _F, _P, _P, _P],
@@ -999,6 +1001,75 @@ def mesh_render_draws(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, draws
                                         C.cast(rot_c, C.c_void_p) if rot_c is not None else None, float(znear), float(color[0]), float(color[1]),
                                         float(color[2]), float(ambient), float(k_d), lx, ly, lz, scr.data_ptr(), nrm.data_ptr(), zbuf.data_ptr(),
                                         _ptr(res.get('color')), _ptr(res.get('face')), _ptr(res.get('depth')), _stream()), 'whmr_mesh_render_draws')
+    if 'screen' in want:
+        res['screen'] = scr[:D * V * 3].view(D, V, 3).clone()
+    return res
+
+
+# a row of the third table of whmr_mesh_render_scene, one per image (include/whmr_hip.h; asserted field by field in csrc/mesh_render.hip as whmr_ground_row)
+RENDER_GROUND_DTYPE = np.dtype({'names': ['draw', 'given', 'y', 'half', 'n', 'dark', 'light', 'reserved'],
+                                'formats': ['<i4', '<i4', '<f4', '<f4', '<i4', '<f4', '<f4', '<i4'], 'offsets': [0, 4, 8, 12, 16, 20, 24, 28], 'itemsize': 32})
+
+
+def _scene_heights(dev, n_draws):
+    """the per-draw height slots of whmr_mesh_render_scene, kept with the draw list's scratch per (device, stream) and grow-only in the same way"""
+    ws = _draw_ws.setdefault((dev, torch.cuda.current_stream(dev).cuda_stream), {'scr': None, 'nrm': None, 'zbuf': None, 'retired': []})
+    h = ws.get('heights')
+    if h is None or h.numel() < n_draws:
+        if h is not None:
+            ws['retired'].append(h)
+        h = ws['heights'] = torch.empty(max(n_draws, 2 * h.numel() if h is not None else 1), dtype=torch.int32, device=dev)
+    return h
+
+
+def mesh_render_scene(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, draws, n_draws, images, n_images, total_pixels, grounds, color, rot=None,
+                      znear=0.05, ambient=0.3, k_d=4 * (1 - 0.2) * (1 - 0.04) / math.pi, light=(0.0, 0.0, 1.0), want=()):
+    """``mesh_render_draws`` with at most one checkerboard ground plane per image (include/whmr_hip.h: whmr_mesh_render_scene).  grounds: the third
+    table as a uint8 DEVICE tensor of ``n_images`` RENDER_GROUND_DTYPE rows (MeshRenderer.plan_grounds packs it).  Returns the dict of
+    ``mesh_render_draws`` -- a plane pixel has the tile's grey in 'color', its depth in 'depth' and -1 in 'face' -- with, if asked for in ``want``,
+    'ground' [total_pixels] int32 = ix * n + iz of the plane's tile or -1, and always 'ground_y' [n_images] fp32: the height of every image's plane
+    (found on the device unless given), NaN where there is none.  The same three launches; nothing is read back."""
+    _dev(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, draws, images, grounds)
+    R, V = verts0.shape[0], verts0.shape[1]
+    F = faces.shape[0]
+    D, NI, total = int(n_draws), int(n_images), int(total_pixels)
+    for v in (verts0, verts1):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == (R, V, 3))
+    assert cam_t.dtype == torch.float32 and cam_t.is_contiguous() and tuple(cam_t.shape) == (R, 3)
+    assert focal.dtype == torch.float32 and focal.is_contiguous() and tuple(focal.shape) == (R, 2)
+    assert faces.dtype == torch.int32 and faces.is_contiguous() and faces.dim() == 2 and faces.shape[1] == 3
+    assert vf_ptr.dtype == torch.int32 and vf_ptr.is_contiguous() and vf_ptr.numel() == V + 1
+    assert vf_idx.dtype == torch.int32 and vf_idx.is_contiguous() and vf_idx.numel() == 3 * F
+    assert draws.dtype == torch.uint8 and draws.is_contiguous() and draws.numel() == D * RENDER_DRAW_DTYPE.itemsize
+    assert images.dtype == torch.uint8 and images.is_contiguous() and images.numel() == NI * RENDER_IMAGE_DTYPE.itemsize
+    assert grounds.dtype == torch.uint8 and grounds.is_contiguous() and grounds.numel() == NI * RENDER_GROUND_DTYPE.itemsize
+    assert R >= 1 and D >= 0 and 1 <= NI <= 65535 and total >= 1 and D * F < 2 ** 31
+    unknown = set(want) - {'color', 'face', 'depth', 'screen', 'ground'}
+    assert not unknown, 'unknown outputs %s' % sorted(unknown)
+    dev = verts0.device
+    scr, nrm, zbuf = _draw_workspace(dev, max(D, 1) * V * 3, total)
+    heights = _scene_heights(dev, max(D, 1))
+    res = {'ground_y': torch.empty(NI, dtype=torch.float32, device=dev)}
+    if 'color' in want:
+        res['color'] = torch.empty(total, 3, dtype=torch.float32, device=dev)
+    if 'face' in want:
+        res['face'] = torch.empty(total, dtype=torch.int32, device=dev)
+    if 'depth' in want:
+        res['depth'] = torch.empty(total, dtype=torch.float32, device=dev)
+    if 'ground' in want:
+        res['ground'] = torch.empty(total, dtype=torch.int32, device=dev)
+    rot_c = None
+    if rot is not None:
+        r = [float(v) for row in rot for v in row]
+        assert len(r) == 9
+        rot_c = (C.c_float * 9)(*r)
+    lx, ly, lz = (float(v) for v in light)
+    _check(lib().whmr_mesh_render_scene(verts0.data_ptr(), _ptr(verts1), R, V, faces.data_ptr(), F, vf_ptr.data_ptr(), vf_idx.data_ptr(), cam_t.data_ptr(),
+                                        focal.data_ptr(), draws.data_ptr(), D, images.data_ptr(), NI, total, grounds.data_ptr(),
+                                        C.cast(rot_c, C.c_void_p) if rot_c is not None else None, float(znear), float(color[0]), float(color[1]),
+                                        float(color[2]), float(ambient), float(k_d), lx, ly, lz, scr.data_ptr(), nrm.data_ptr(), zbuf.data_ptr(),
+                                        heights.data_ptr(), _ptr(res.get('color')), _ptr(res.get('face')), _ptr(res.get('depth')), _ptr(res.get('ground')),
+                                        res['ground_y'].data_ptr(), _stream()), 'whmr_mesh_render_scene')
     if 'screen' in want:
         res['screen'] = scr[:D * V * 3].view(D, V, 3).clone()
     return res

@@ -25,6 +25,20 @@
 // direction TO the light, k_d = n_lights (1 - metallic) (1 - 0.04) / pi with metallic 0.2, n_lights 4: the diffuse term of the glTF metallic-roughness
 // model.  The specular lobe (default roughness 1.0) is left out.  alphaMode 'OPAQUE': alpha does nothing in the reference and is no parameter.
 // Background pixels keep the frame's bytes (the valid mask of :138-140, not a blend); uint8 = round-half-even(255 * rgb) of the fp32 colour.
+//
+// Ground plane (renderer_cam.py:53,95-104: add_ground_plane, on in both side views of render_image_group; whmr_mesh_render_scene below).  The reference
+// adds get_checkerboard_plane() -- a PARE helper that is not in the reference tree -- lifted to the mesh's lowest point mesh.bounds[0, 1]; the mesh is
+// turned by S, the plane is not (:79-82 against :100-104).  The plane is therefore DEFINED here: the horizontal square |q_x| <= half, |q_z| <= half at
+// q_y = h in the world frame (y up), n x n tiles of side 2 half / n, no thickness, seen from both sides, flat UNLIT greys (pyrender would light the
+// tiles: a stated deviation): tile (ix, iz) is `dark` where ix + iz is even, else `light`.  h = the lowest world-frame y of the owning draw's mesh:
+// S turns about y and D negates y, so h = -max_v p_y over the mesh-frame vertices (NaN vertices skipped), or a height the caller gives.  A plane
+// belongs to ONE draw: its camera is that draw's row (cam_t, focal), its image's centre and the call's rot -- the reference moves the camera by t' and
+// leaves mesh and plane at the origin, so the floor is centred under that person's root.  It is never triangulated: the resolve pass intersects the
+// pixel's ray with it.  From  (X, Y, Z) = D R^T q + t  follows  q = R D ((X, Y, Z) - t);  pixel (j, i) looks along (a, b, 1) Z with
+// a = (i + 0.5 - cx) / fx, b = (j + 0.5 - cy) / fy, hence  q = Z w + o,  w = R D (a, b, 1),  o = -R D t,  and the plane is met at depth
+// Z_g = (h - o_y) / w_y.  It covers the pixel iff Z_g is finite, Z_g > znear and 0 <= ix, iz < n with ix = floor((q_x + half) / tile),
+// iz = floor((q_z + half) / tile); it owns the pixel iff it covers it and no face does or Z_g < the winning face's depth (a tie goes to the mesh).
+// A plane pixel counts as covered (the rend_depth > 0 mask of :138): colour = the tile's grey, depth = Z_g, face id -1, `ground` = ix n + iz.
 #include "common.h"
 
 struct mesh_cam { float cx, cy, sc, ss; int has_rot; float r[9]; };
@@ -359,14 +373,11 @@ struct mesh_draw_targets {
     __device__ __forceinline__ mesh_target target(int img) const { return mesh_target{images[img].H, images[img].W, (long)images[img].pix_off}; }
 };
 
-// Launch 1: z-buffer clear of all images + one thread per (draw, vertex); the centre comes from the draw's image, the angle from the draw.
-__global__ __launch_bounds__(256) void mesh_draw_vertex_kernel(const float* __restrict__ verts0, const float* __restrict__ verts1, const int32_t* __restrict__ faces,
-                                                               const int32_t* __restrict__ vf_ptr, const int32_t* __restrict__ vf_idx,
-                                                               const float* __restrict__ cam_t, const float* __restrict__ focal, float* __restrict__ scr,
-                                                               float* __restrict__ nrm, unsigned long long* __restrict__ zbuf, int D, int V, mesh_draw_targets tg,
-                                                               mesh_cam c) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx < tg.total) zbuf[idx] = ~0ull;
+// One (draw, vertex) of launch 1, one code path for the draw list and the scene: the centre comes from the draw's image, the angle from the draw.
+__device__ __forceinline__ void mesh_draw_vertex(const float* __restrict__ verts0, const float* __restrict__ verts1, const int32_t* __restrict__ faces,
+                                                 const int32_t* __restrict__ vf_ptr, const int32_t* __restrict__ vf_idx, const float* __restrict__ cam_t,
+                                                 const float* __restrict__ focal, float* __restrict__ scr, float* __restrict__ nrm, long idx, int D, int V,
+                                                 const mesh_draw_targets& tg, mesh_cam c) {
     if (idx >= (long)D * V) return;
     const int d = (int)(idx / V), v = (int)(idx - (long)d * V);
     const int img = tg.image(d);
@@ -375,6 +386,17 @@ __global__ __launch_bounds__(256) void mesh_draw_vertex_kernel(const float* __re
     c.cx = tg.images[img].cx; c.cy = tg.images[img].cy; c.sc = dr.side_cos; c.ss = dr.side_sin;
     mesh_vertex((dr.verts_set ? verts1 : verts0) + (size_t)dr.row * V * 3, v, faces, vf_ptr, vf_idx, cam_t + (size_t)dr.row * 3, focal + (size_t)dr.row * 2, c,
                 scr + idx * 3, nrm + idx * 3);
+}
+
+// Launch 1: z-buffer clear of all images + one thread per (draw, vertex).
+__global__ __launch_bounds__(256) void mesh_draw_vertex_kernel(const float* __restrict__ verts0, const float* __restrict__ verts1, const int32_t* __restrict__ faces,
+                                                               const int32_t* __restrict__ vf_ptr, const int32_t* __restrict__ vf_idx,
+                                                               const float* __restrict__ cam_t, const float* __restrict__ focal, float* __restrict__ scr,
+                                                               float* __restrict__ nrm, unsigned long long* __restrict__ zbuf, int D, int V, mesh_draw_targets tg,
+                                                               mesh_cam c) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < tg.total) zbuf[idx] = ~0ull;
+    mesh_draw_vertex(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, scr, nrm, idx, D, V, tg, c);
 }
 
 // Launch 2: one lane per (draw, face).
@@ -427,6 +449,205 @@ extern "C" int whmr_mesh_render_draws(const float* verts0, const float* verts1, 
     const long mean_plane = (total_pixels + NI - 1) / NI;
     hipLaunchKernelGGL(mesh_draw_resolve_kernel, dim3((unsigned)((mean_plane + 255) / 256), (unsigned)NI), dim3(256), 0, st, scr, nrm, faces,
                        (const unsigned long long*)zbuf, color_out, face_out, depth_out, V, F, tg, m);
+    WHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// Scene form: the draw list plus at most one checkerboard ground plane per image (see the header).  A third device table has one row per image
+// (whmr_amd._lib.RENDER_GROUND_DTYPE restates it, tests/test_mesh_ground_cpu.py holds the two sides together through the static_asserts below).
+struct whmr_ground_row {
+    int32_t draw;                               // the draw that owns the plane: its row is the camera, its mesh gives the height; -1 = no plane
+    int32_t given;                              // 0: y = the lowest world-frame point of the owning draw's mesh, found on the device; 1: y below
+    float y;                                    // the plane's height in the world frame (y up), read when given
+    float half;                                 // half the side of the square, > 0
+    int32_t n;                                  // tiles per side, >= 1
+    float dark, light;                          // grey of the tiles with ix + iz even / odd, 0..1
+    int32_t reserved;
+};
+static_assert(sizeof(whmr_ground_row) == 32, "table layout");
+static_assert(offsetof(whmr_ground_row, draw) == 0, "table layout");
+static_assert(offsetof(whmr_ground_row, given) == 4, "table layout");
+static_assert(offsetof(whmr_ground_row, y) == 8, "table layout");
+static_assert(offsetof(whmr_ground_row, half) == 12, "table layout");
+static_assert(offsetof(whmr_ground_row, n) == 16, "table layout");
+static_assert(offsetof(whmr_ground_row, dark) == 20, "table layout");
+static_assert(offsetof(whmr_ground_row, light) == 24, "table layout");
+static_assert(offsetof(whmr_ground_row, reserved) == 28, "table layout");
+
+// max_v p_y of a draw as an integer maximum: the key grows with the float (negative floats with their magnitude bits flipped), so an atomic max
+// of keys is the exact maximum whatever order the lanes arrive in.  MESH_NO_HEIGHT is below every key of a number and decodes to a NaN.
+#define MESH_NO_HEIGHT ((int32_t)0x80000000)
+__device__ __forceinline__ int32_t mesh_height_key(float f) { const int32_t i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
+__device__ __forceinline__ float mesh_height_of(int32_t k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
+
+struct mesh_scene {
+    const whmr_ground_row* grounds;             // [NI]
+    int32_t* heights;                           // [D] scratch: key of max_v p_y of every draw whose plane asks for it
+    int32_t* ground_out;                        // [total_pixels] or null
+    float* ground_y;                            // [NI]
+    int D;
+    // the plane of image img: its owning draw, or -1 (no plane, or a row the host would have refused: nothing is read through it)
+    __device__ __forceinline__ int owner(int img, const mesh_draw_targets& tg) const {
+        const whmr_ground_row& g = grounds[img];
+        const bool ok = (unsigned)g.draw < (unsigned)D && g.n >= 1 && g.half > 0.f && tg.image(g.draw) == img;
+        return ok ? g.draw : -1;
+    }
+};
+
+// Launch 1 of the scene: as the draw list's, and the height slots are cleared beside the z-buffer.
+__global__ __launch_bounds__(256) void mesh_scene_vertex_kernel(const float* __restrict__ verts0, const float* __restrict__ verts1, const int32_t* __restrict__ faces,
+                                                                const int32_t* __restrict__ vf_ptr, const int32_t* __restrict__ vf_idx,
+                                                                const float* __restrict__ cam_t, const float* __restrict__ focal, float* __restrict__ scr,
+                                                                float* __restrict__ nrm, unsigned long long* __restrict__ zbuf, int D, int V, mesh_draw_targets tg,
+                                                                mesh_cam c, int32_t* __restrict__ heights) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < tg.total) zbuf[idx] = ~0ull;
+    if (idx < D) heights[idx] = MESH_NO_HEIGHT;
+    mesh_draw_vertex(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, scr, nrm, idx, D, V, tg, c);
+}
+
+// Launch 2 of the scene: lane idx < D * V also looks at vertex idx: if its draw owns a plane without a given height, p_y enters the draw's maximum --
+// reduced over the wave first (the lanes of a wave nearly always share the draw), one atomic per wave and draw.  Every lane of the wave comes here.
+__device__ __forceinline__ void mesh_heights(const float* __restrict__ verts0, const float* __restrict__ verts1, long idx, int V, const mesh_draw_targets& tg,
+                                             const mesh_scene& sc) {
+    int d = -1;
+    int32_t key = MESH_NO_HEIGHT;
+    if (idx < (long)sc.D * V) {
+        const int dd = (int)(idx / V), v = (int)(idx - (long)dd * V);
+        const int img = tg.image(dd);
+        if (img >= 0 && !sc.grounds[img].given && sc.owner(img, tg) == dd) {
+            d = dd;
+            const whmr_render_draw& dr = tg.draws[dd];
+            const float py = ((dr.verts_set ? verts1 : verts0) + (size_t)dr.row * V * 3)[(size_t)v * 3 + 1];
+            if (py == py) key = mesh_height_key(py);                              // a NaN vertex is skipped
+        }
+    }
+    const unsigned long long any = __ballot(d >= 0);
+    if (!any) return;                                                             // wave-uniform: no lane of this wave feeds a plane
+    const int d0 = __shfl(d, __ffsll((long long)any) - 1, 64);
+    int32_t k = d == d0 ? key : MESH_NO_HEIGHT;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int32_t other = __shfl_xor(k, off, 64);
+        k = other > k ? other : k;
+    }
+    if ((threadIdx.x & 63) == 0 && k != MESH_NO_HEIGHT) atomicMax(sc.heights + d0, k);
+    if (d >= 0 && d != d0 && key != MESH_NO_HEIGHT) atomicMax(sc.heights + d, key);   // the few lanes of a wave that straddles two draws
+}
+__global__ __launch_bounds__(256) void mesh_scene_faces_kernel(const float* __restrict__ verts0, const float* __restrict__ verts1, const float* __restrict__ scr,
+                                                               const int32_t* __restrict__ faces, unsigned long long* __restrict__ zbuf, int V, int F, float znear,
+                                                               mesh_draw_targets tg, mesh_scene sc) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    mesh_heights(verts0, verts1, idx, V, tg, sc);
+    mesh_faces(scr, faces, zbuf, idx, (long)sc.D * F, V, F, znear, tg);
+}
+
+// The plane of one image as the resolve pass needs it (see the header): q = Z w + o with w = R D (a, b, 1), o = -R D t.
+struct mesh_plane { bool on; float h, half, tile, n, dark, light, fx, fy, ox, oy, oz; };
+__device__ __forceinline__ mesh_plane mesh_plane_setup(int img, const mesh_draw_targets& tg, const mesh_scene& sc, const float* __restrict__ cam_t,
+                                                       const float* __restrict__ focal, const mesh_cam& c) {
+    mesh_plane p{};
+    const int d = sc.owner(img, tg);
+    if (d < 0) return p;
+    const whmr_ground_row g = sc.grounds[img];
+    p.h = g.given ? g.y : -mesh_height_of(sc.heights[d]);
+    if (!(p.h == p.h)) return p;                                                  // no finite vertex (or a NaN given): no plane
+    const int row = tg.draws[d].row;
+    const float tx = -cam_t[(size_t)row * 3], ty = cam_t[(size_t)row * 3 + 1], tz = cam_t[(size_t)row * 3 + 2];      // -D t
+    p.ox = tx; p.oy = ty; p.oz = tz;
+    if (c.has_rot) {
+        p.ox = (c.r[0] * tx + c.r[1] * ty) + c.r[2] * tz;
+        p.oy = (c.r[3] * tx + c.r[4] * ty) + c.r[5] * tz;
+        p.oz = (c.r[6] * tx + c.r[7] * ty) + c.r[8] * tz;
+    }
+    p.fx = focal[(size_t)row * 2]; p.fy = focal[(size_t)row * 2 + 1];
+    p.half = g.half; p.n = (float)g.n; p.tile = 2.f * g.half / (float)g.n; p.dark = g.dark; p.light = g.light;
+    p.on = true;
+    return p;
+}
+// pixel (x, y) against the plane: true = the plane covers it, at depth Z in tile (ix, iz)
+__device__ __forceinline__ bool mesh_plane_hit(const mesh_plane& p, const mesh_cam& c, float cx, float cy, int x, int y, float znear, float& Z, int& ix, int& iz) {
+    const float a = ((float)x + 0.5f - cx) / p.fx, b = -(((float)y + 0.5f - cy) / p.fy);
+    float wx = a, wy = b, wz = -1.f;
+    if (c.has_rot) {
+        wx = (c.r[0] * a + c.r[1] * b) - c.r[2];
+        wy = (c.r[3] * a + c.r[4] * b) - c.r[5];
+        wz = (c.r[6] * a + c.r[7] * b) - c.r[8];
+    }
+    Z = (p.h - p.oy) / wy;
+    const float fi = floorf((__fmaf_rn(Z, wx, p.ox) + p.half) / p.tile), fk = floorf((__fmaf_rn(Z, wz, p.oz) + p.half) / p.tile);
+    const bool hit = fabsf(Z) < __builtin_inff() && Z > znear && fi >= 0.f && fi < p.n && fk >= 0.f && fk < p.n;     // every comparison is false for a NaN
+    ix = hit ? (int)fi : 0; iz = hit ? (int)fk : 0;
+    return hit;
+}
+
+// Launch 3 of the scene: the draw list's resolve; an image with a plane (one block-uniform branch) also intersects the pixel's ray with it.
+__global__ __launch_bounds__(256) void mesh_scene_resolve_kernel(const float* __restrict__ scr, const float* __restrict__ nrm, const int32_t* __restrict__ faces,
+                                                                 const unsigned long long* __restrict__ zbuf, float* __restrict__ color_out,
+                                                                 int32_t* __restrict__ face_out, float* __restrict__ depth_out, const float* __restrict__ cam_t,
+                                                                 const float* __restrict__ focal, int V, int F, float znear, mesh_draw_targets tg, mesh_shade m,
+                                                                 mesh_cam c, mesh_scene sc) {
+    const int img = (int)blockIdx.y;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    if (!tg.image_ok(img)) {
+        if (first) sc.ground_y[img] = __builtin_nanf("");
+        return;
+    }
+    const whmr_render_image im = tg.images[img];
+    const mesh_plane pl = mesh_plane_setup(img, tg, sc, cam_t, focal, c);
+    if (first) sc.ground_y[img] = pl.on ? pl.h : __builtin_nanf("");
+    const long plane = (long)im.H * im.W;
+    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < plane; r += (long)gridDim.x * 256) {
+        const int y = (int)(r / im.W), x = (int)(r - (long)y * im.W);
+        const long at = im.pix_off + r;
+        mesh_sample s = mesh_resolve(zbuf[at], x, y, scr, nrm, faces, V, F, m);
+        int tile = -1;
+        if (pl.on) {
+            float Z;
+            int ix, iz;
+            if (mesh_plane_hit(pl, c, im.cx, im.cy, x, y, znear, Z, ix, iz) && (!s.hit || Z < s.depth)) {
+                const float grey = ((ix + iz) & 1) ? pl.light : pl.dark;
+                s = mesh_sample{-1, grey, grey, grey, Z, true};
+                tile = ix * (int)pl.n + iz;
+            }
+        }
+        mesh_store(s, im.out + y * im.out_row_stride + (long)x * 3, im.frame ? im.frame + y * im.frame_row_stride + (long)x * 3 : nullptr, at, color_out,
+                   face_out, depth_out);
+        if (sc.ground_out) sc.ground_out[at] = tile;
+    }
+}
+
+// The arguments of whmr_mesh_render_draws, and: grounds: DEVICE table of NI whmr_ground_row; heights [max(D, 1)] int32 scratch; ground_out
+// [total_pixels] int32 (ix * n + iz of the plane's tile, -1 elsewhere) or null; ground_y [NI] fp32: the height of every image's plane, NaN = none.
+// A table without a plane gives the bytes of whmr_mesh_render_draws.  Three launches, no allocation, no synchronisation; bit-reproducible.
+extern "C" int whmr_mesh_render_scene(const float* verts0, const float* verts1, int R, int V, const int32_t* faces, int F, const int32_t* vf_ptr,
+                                      const int32_t* vf_idx, const float* cam_t, const float* focal, const void* draws, int D, const void* images, int NI,
+                                      long total_pixels, const void* grounds, const float* rot, float znear, float base_r, float base_g, float base_b,
+                                      float ambient, float k_d, float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, int32_t* heights,
+                                      float* color_out, int32_t* face_out, float* depth_out, int32_t* ground_out, float* ground_y, void* stream) {
+    if (R <= 0 || V <= 0 || F <= 0 || D < 0 || NI <= 0 || NI > 65535 || total_pixels <= 0 || (long)D * F > 0x7fffffffL || !grounds || !heights || !ground_y)
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    mesh_cam c{0.f, 0.f, 1.f, 0.f, rot != nullptr, {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}};
+    if (rot)
+        for (int k = 0; k < 9; ++k) c.r[k] = rot[k];
+    mesh_shade m{base_r, base_g, base_b, ambient, k_d, lx, ly, lz};
+    mesh_draw_targets tg{(const whmr_render_draw*)draws, (const whmr_render_image*)images, R, NI, verts1 != nullptr, total_pixels};
+    mesh_scene sc{(const whmr_ground_row*)grounds, heights, ground_out, ground_y, D};
+    const long n0 = (long)D * V > total_pixels ? (long)D * V : total_pixels;                // >= D: the height slots are cleared by the same grid
+    hipLaunchKernelGGL(mesh_scene_vertex_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, scr,
+                       nrm, (unsigned long long*)zbuf, D, V, tg, c, heights);
+    WHMR_CHECK_LAUNCH();
+    if (D > 0) {
+        const long n1 = (long)D * (F > V ? F : V);
+        hipLaunchKernelGGL(mesh_scene_faces_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, verts0, verts1, scr, faces, (unsigned long long*)zbuf,
+                           V, F, znear, tg, sc);
+        WHMR_CHECK_LAUNCH();
+    }
+    const long mean_plane = (total_pixels + NI - 1) / NI;
+    hipLaunchKernelGGL(mesh_scene_resolve_kernel, dim3((unsigned)((mean_plane + 255) / 256), (unsigned)NI), dim3(256), 0, st, scr, nrm, faces,
+                       (const unsigned long long*)zbuf, color_out, face_out, depth_out, cam_t, focal, V, F, znear, tg, m, c, sc);
     WHMR_CHECK_LAUNCH();
     return 0;
 }

@@ -112,36 +112,39 @@ def infer_frame(model, frame_u8, dets, with_full_image=True, full_image='torch')
 
 
 @torch.no_grad()
-def render_frame(out, frame_u8, renderer, per_person=False):
+def render_frame(out, frame_u8, renderer, per_person=False, ground=False):
     """The picture of a frame (tester.py:176-214, overlay panel): ``local_smpl_vertices`` of the vis_dict ``out`` drawn over ``frame_u8`` with
     ``pred_cam_t`` / ``focal_length``, identity camera rotation (tester.py:194) and the frame centre (:185) by ``renderer``
-    (utils.renderer_cam.MeshRenderer).  uint8 [H, W, 3] with all persons in one depth buffer, or [P, H, W, 3] with per_person.  No host sync."""
+    (utils.renderer_cam.MeshRenderer).  uint8 [H, W, 3] with all persons in one depth buffer, or [P, H, W, 3] with per_person.  ground: True (or a
+    height) puts the checkerboard ground plane under every person; a plane has one person's camera, so it needs per_person or a single person
+    (ValueError otherwise).  No host sync."""
     if isinstance(frame_u8, np.ndarray):
         frame_u8 = torch.from_numpy(np.ascontiguousarray(frame_u8)).cuda()
-    return renderer.render(frame_u8, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], per_person=per_person)
+    return renderer.render(frame_u8, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], per_person=per_person, ground=ground)
 
 
 @torch.no_grad()
-def render_clip(out, frames, renderer, frame_index, per_person=False):
+def render_clip(out, frames, renderer, frame_index, per_person=False, ground=False):
     """``render_frame`` for a whole clip in one launch group (MeshRenderer.render_clip): the rows of the vis_dict ``out`` drawn over their frames.
     frames: [F, H, W, 3] or a list of frames (device tensors; numpy is uploaded); frame_index: the frame of every row as HOST integers.  Returns a
-    list of F uint8 images, each equal to ``render_frame`` on that frame's rows (a frame without rows: its own bytes), or P images with per_person."""
+    list of F uint8 images, each equal to ``render_frame`` on that frame's rows (a frame without rows: its own bytes), or P images with per_person.
+    ground as for ``render_frame``, in the same launch group."""
     if isinstance(frames, np.ndarray):
         frames = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
     elif not torch.is_tensor(frames):
         frames = [torch.from_numpy(np.ascontiguousarray(f)).cuda() if isinstance(f, np.ndarray) else f for f in frames]
-    return renderer.render_clip(frames, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], frame_index, per_person=per_person)
+    return renderer.render_clip(frames, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], frame_index, per_person=per_person, ground=ground)
 
 
 class FramePipeline:
     """infer_frame with the model call (cam_model + W-HMR forward, ~200 launches) replayed from a HIP graph per (number of persons,
     full-image size): at one to a few persons per frame the eager path is bound by Python launch overhead, not by the GPU.
     With ``renderer`` (utils.renderer_cam.MeshRenderer) the call returns (vis_dict, image): the overlay is launched right behind the replayed graph on
-    the same stream, with no host sync between model and picture."""
+    the same stream, with no host sync between model and picture; ``ground`` is handed to ``render_frame``."""
 
-    def __init__(self, model, with_full_image=True, renderer=None, per_person=False, full_image='torch'):
+    def __init__(self, model, with_full_image=True, renderer=None, per_person=False, full_image='torch', ground=False):
         self.model, self.with_full_image, self._graphs = model, with_full_image, {}
-        self.renderer, self.per_person, self.full_image = renderer, per_person, full_image
+        self.renderer, self.per_person, self.full_image, self.ground = renderer, per_person, full_image, ground
 
     @torch.no_grad()
     def __call__(self, frame_u8, dets):
@@ -158,7 +161,7 @@ class FramePipeline:
         out = g(**call)
         if self.renderer is None:
             return out
-        return out, render_frame(out, frame_u8, self.renderer, self.per_person)
+        return out, render_frame(out, frame_u8, self.renderer, self.per_person, self.ground)
 
 
 # ----------------------------------------------------------------------------- clip inference: all persons of many frames in one model call
@@ -269,11 +272,11 @@ class ClipPipeline:
     ``render_clip`` launch group for the whole clip, each image what ``render_frame`` draws over that frame's rows, behind the replayed graph on the
     same stream, no host sync; a frame without detections comes back as a copy of itself; per_person: [P images], one person each.  With
     ``smoother`` (a TrackSmoother) and per-call ``track_ids`` the smoothing stage (one filter launch + two SMPL calls) runs behind the replayed graph on the same stream, outside the graph -- its table changes per clip, like the input preparation --
-    and the renderer draws the smoothed rows; the padding rows never enter a track."""
+    and the renderer draws the smoothed rows; the padding rows never enter a track.  ``ground`` is handed to ``render_clip``."""
 
-    def __init__(self, model, with_full_image=True, person_bucket=8, renderer=None, smoother=None, per_person=False):
+    def __init__(self, model, with_full_image=True, person_bucket=8, renderer=None, smoother=None, per_person=False, ground=False):
         self.model, self.with_full_image, self.person_bucket, self.renderer, self._graphs = model, with_full_image, person_bucket, renderer, {}
-        self.smoother, self.per_person = smoother, per_person
+        self.smoother, self.per_person, self.ground = smoother, per_person, ground
 
     @torch.no_grad()
     def __call__(self, frames, dets_per_frame, track_ids=None):
@@ -294,7 +297,7 @@ class ClipPipeline:
         if self.renderer is None:
             return out
         index = np.repeat(np.arange(len(dets_per_frame)), [len(d) for d in dets_per_frame])       # from the detections: the host has them
-        return out, render_clip(out, kw['frames'], self.renderer, index, self.per_person)
+        return out, render_clip(out, kw['frames'], self.renderer, index, self.per_person, self.ground)
 
 
 # ----------------------------------------------------------------------------- temporal smoothing of tracked persons

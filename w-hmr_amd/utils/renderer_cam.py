@@ -6,6 +6,8 @@ demo/tester.py:176-214 uses it, restated on csrc/mesh_render.hip -- an Instinct 
     imgs = r.render(frame_u8, verts, cam_t, focal, per_person=True)  # uint8 [P, H, W, 3]: one person per image, as the reference draws them
     imgs = r.render_clip(frames, verts, cam_t, focal, frame_index)  # a clip: F images, row i drawn into frame frame_index[i]; one call, three launches
     strips = render_clip_groups(frames, cam_t, verts, local_verts, None, focal, frame_index, r)     # render_image_group for every person of the clip
+    imgs = r.render(None, verts, cam_t, focal, size=(H, W), per_person=True, sideview_angle=270, ground=True)     # a checkerboard floor under every person
+    export_obj('person_rot.obj', verts[0], smpl_faces, sideview_angle=270)                          # the mesh as the reference's --save_obj writes it
 
 Camera, coverage rule and the shading model (pyrender's shader is third-party: the model is defined by this package, diffuse only) are written out in
 csrc/mesh_render.hip and docs/kernels.md.  HIP only: CPU tensors raise RuntimeError, like every other entry point here.
@@ -18,6 +20,17 @@ import torch
 from .. import _lib as L
 
 DEFAULT_COLOR = (0.65, 0.74, 0.86)      # a light steel blue chosen for this package (bright enough that the four lights do not clip it to white)
+# The checkerboard ground plane (csrc/mesh_render.hip): a 4 m square of 9 x 9 tiles.  The tile greys are recalled from PARE's get_checkerboard_plane,
+# which is not in the reference tree: unverified, so they are parameters of MeshRenderer.
+GROUND_HALF, GROUND_TILES = 2.0, 9
+GROUND_DARK, GROUND_LIGHT = 35 / 255, 220 / 255
+
+
+def _ground_height(ground):
+    """the ``ground`` argument of the render calls -> None (no plane), True (at the mesh's lowest point, found on the device) or a float height"""
+    if ground is None or ground is False:
+        return None
+    return True if ground is True else float(ground)
 
 
 def vertex_face_csr(faces, n_verts):
@@ -32,8 +45,9 @@ def vertex_face_csr(faces, n_verts):
 
 
 class MeshRenderer:
-    def __init__(self, faces, color=DEFAULT_COLOR):
-        """faces: [F, 3] integer face table (numpy / tensor / list); color: (r, g, b) in 0..1, the material's base colour."""
+    def __init__(self, faces, color=DEFAULT_COLOR, ground_colors=(GROUND_DARK, GROUND_LIGHT)):
+        """faces: [F, 3] integer face table (numpy / tensor / list); color: (r, g, b) in 0..1, the material's base colour; ground_colors: (dark, light)
+        greys in 0..1 of the ground plane's tiles."""
         f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
         f = np.ascontiguousarray(f.reshape(-1, 3).astype(np.int64))
         if f.size == 0 or f.min() < 0:
@@ -42,6 +56,7 @@ class MeshRenderer:
         self.faces = torch.from_numpy(f.astype(np.int32))
         self.color = tuple(float(c) for c in color)
         assert len(self.color) == 3
+        self.ground_colors = (float(ground_colors[0]), float(ground_colors[1]))
         self._host = f
         self._dev = {}
 
@@ -54,12 +69,20 @@ class MeshRenderer:
         return t
 
     @torch.no_grad()
-    def render(self, frame_u8, verts, cam_t, focal, center=None, rot=None, sideview_angle=0, per_person=False, want=(), size=None, znear=0.05):
+    def render(self, frame_u8, verts, cam_t, focal, center=None, rot=None, sideview_angle=0, per_person=False, want=(), size=None, znear=0.05,
+               ground=False):
         """frame_u8: uint8 [H, W, 3] on the device, or None for a black background of ``size`` = (H, W); verts [P, V, 3] in the mesh frame
         (``local_smpl_vertices`` / ``smpl_vertices``), cam_t [P, 3] (``pred_cam_t``), focal [P] or [P, 2] (``focal_length``), all device tensors;
         center (cx, cy), default (W // 2, H // 2) (tester.py:185); rot: camera_rotation as 3 x 3 HOST values (the demo passes the identity,
         tester.py:194) or None; sideview_angle in degrees about Y.  want: any of 'color', 'face', 'depth', 'screen' -> a dict (see _lib.mesh_render).
+        ground: True puts the checkerboard ground plane (csrc/mesh_render.hip) under every person, at the lowest point of that person's mesh,
+        found on the device; a float puts it at that world-frame height (y up).  A plane belongs to one person's camera, so ``ground`` needs
+        per_person=True or a single row (ValueError otherwise); the dict then also has 'ground_y' [P] (the heights used, NaN = no plane) and, if
+        asked for in ``want``, 'ground' (ix * n + iz of the plane's tile, -1 elsewhere); a plane pixel has -1 in 'face'.
         Nothing here waits for the device: the call can be captured in a HIP graph or follow a replayed one on the same stream."""
+        height = _ground_height(ground)
+        if height is not None and not per_person and verts.shape[0] != 1:
+            raise ValueError('a ground plane belongs to one person: %d rows share the image (per_person=True gives every person an image)' % verts.shape[0])
         for t in (frame_u8, verts, cam_t, focal):
             if t is not None and not (torch.is_tensor(t) and t.is_cuda):
                 raise RuntimeError('MeshRenderer.render needs HIP device tensors; there is no CPU fallback')
@@ -81,9 +104,27 @@ class MeshRenderer:
             if rot.is_cuda:
                 raise RuntimeError('rot is read on the host (it enters the launch as kernel arguments): pass a CPU tensor, numpy array or nested list')
             rot = rot.reshape(3, 3).tolist()
+        if height is not None:
+            return self._render_grounded(frame_u8, verts, cam_t, focal, center, rot, sideview_angle, per_person, want, (int(H), int(W)), znear, height)
         faces, ptr, idx = self._tables(verts.device, V)
         return L.mesh_render(verts, faces, ptr, idx, cam_t, focal, center, frame_u8, (H, W), self.color, rot=rot, sideview_angle=sideview_angle,
                              per_person=per_person, znear=znear, want=want)
+
+    def _render_grounded(self, frame_u8, verts, cam_t, focal, center, rot, sideview_angle, per_person, want, size, znear, height):
+        """``render`` with a ground plane: one image and one draw per person through the scene form of the draw list"""
+        P = verts.shape[0]
+        out = torch.empty((P,) + size + (3,), dtype=torch.uint8, device=verts.device)
+        draws = [(p, 0, p, sideview_angle) for p in range(P)]
+        images, table, total = self.plan_draws([size] * P, draws, centers=[center] * P, n_rows=P)
+        grounds = self.plan_grounds(P, draws, [(p, p, None if height is True else height) for p in range(P)])
+        res = self._run_draws(images, table, total, [frame_u8] * P, list(out.unbind(0)), verts, None, cam_t, focal, rot, znear, want, grounds=grounds)
+        img = out if per_person else out[0]
+        if not want:
+            return img
+        res = {k: v if k in ('screen', 'ground_y') else v.view((P,) + size + tuple(v.shape[1:])) for k, v in res.items()}
+        if not per_person:
+            res = {k: v if k in ('screen', 'ground_y') else v[0] for k, v in res.items()}
+        return dict(res, image=img)
 
     # ---- draw list: many mesh instances into many images in one call (csrc/mesh_render.hip: whmr_mesh_render_draws)
     def plan_draws(self, sizes, draws, centers=None, frame_strides=None, out_strides=None, have_verts1=False, n_rows=None):
@@ -123,34 +164,72 @@ class MeshRenderer:
             table[d] = (int(row), int(vset), int(img), math.cos(a), math.sin(a), (0, 0, 0))
         return images, table, int(planes.sum())
 
-    def upload_draws(self, images, table, backgrounds, outputs, device):
+    def plan_grounds(self, n_images, draws, grounds, half=GROUND_HALF, n=GROUND_TILES):
+        """The third table of whmr_mesh_render_scene, one row per image, from what the host knows.  draws: the draw list given to ``plan_draws``;
+        grounds: per plane (image, draw, height) or (image, draw, height, half, n) -- the plane of ``image`` belongs to ``draw`` (index into
+        ``draws``), which gives its camera and, with height None, its height (the lowest point of the draw's mesh, found on the device); half: half
+        the side of the square in metres, n: tiles per side.  Returns numpy records of _lib.RENDER_GROUND_DTYPE (draw = -1: no plane) with this
+        renderer's ground_colors.  ValueError: an image or draw index out of range, two planes on one image, a plane whose draw targets another
+        image, a plane on an image that several draws share (a plane has one camera), n < 1, half <= 0."""
+        n_images = int(n_images)
+        table = np.zeros(n_images, dtype=L.RENDER_GROUND_DTYPE)
+        table['draw'] = -1
+        per_image = np.bincount([int(d[2]) for d in draws if 0 <= int(d[2]) < n_images], minlength=n_images)
+        for g in grounds:
+            img, d, height = int(g[0]), int(g[1]), g[2]
+            g_half, g_n = (float(g[3]), int(g[4])) if len(g) > 3 else (float(half), int(n))
+            if not 0 <= img < n_images:
+                raise ValueError('a ground plane names image %d of %d' % (img, n_images))
+            if not 0 <= d < len(draws):
+                raise ValueError('the ground plane of image %d names draw %d of %d' % (img, d, len(draws)))
+            if table['draw'][img] >= 0:
+                raise ValueError('image %d has two ground planes' % img)
+            if int(draws[d][2]) != img:
+                raise ValueError('the ground plane of image %d belongs to draw %d, which targets image %d' % (img, d, int(draws[d][2])))
+            if per_image[img] != 1:
+                raise ValueError('image %d is shared by %d draws: a ground plane belongs to the camera of one' % (img, per_image[img]))
+            if g_n < 1 or not g_half > 0:
+                raise ValueError('a ground plane has n >= 1 tiles per side and half > 0, got n = %d, half = %g' % (g_n, g_half))
+            table[img] = (d, 0 if height is None else 1, 0.0 if height is None else float(height), g_half, g_n, self.ground_colors[0],
+                          self.ground_colors[1], 0)
+        return table
+
+    def upload_draws(self, images, table, backgrounds, outputs, device, grounds=None):
         """fill in the pointers of the planned tables (backgrounds: per image a uint8 device tensor or None = black; outputs: the tensors written) and
-        send both tables up in one non-blocking copy from pinned memory -> (images, draws) as uint8 device tensors.  The caller keeps the
-        backgrounds and outputs alive for as long as the tables are drawn with."""
+        send the tables up in one non-blocking copy from pinned memory -> (images, draws) as uint8 device tensors, or (images, draws, grounds) with
+        the table of ``plan_grounds``.  The caller keeps the backgrounds and outputs alive for as long as the tables are drawn with."""
         images['frame'] = [0 if b is None else b.data_ptr() for b in backgrounds]
         images['out'] = [o.data_ptr() for o in outputs]
-        n_img = images.nbytes
-        host = torch.empty(n_img + table.nbytes, dtype=torch.uint8).pin_memory()
+        n_img, n_draw = images.nbytes, images.nbytes + table.nbytes
+        host = torch.empty(n_draw + (0 if grounds is None else grounds.nbytes), dtype=torch.uint8).pin_memory()
         host.numpy()[:n_img] = images.view(np.uint8)
-        host.numpy()[n_img:] = table.view(np.uint8)
-        both = host.to(device, non_blocking=True)
-        return both[:n_img], both[n_img:]
+        host.numpy()[n_img:n_draw] = table.view(np.uint8)
+        if grounds is None:
+            both = host.to(device, non_blocking=True)
+            return both[:n_img], both[n_img:]
+        host.numpy()[n_draw:] = grounds.view(np.uint8)
+        up = host.to(device, non_blocking=True)
+        return up[:n_img], up[n_img:n_draw], up[n_draw:]
 
     @torch.no_grad()
     def run_draws(self, tables, n_images, n_draws, total_pixels, verts0, verts1, cam_t, focal, rot=None, znear=0.05, want=()):
         """the launch group over uploaded tables (``upload_draws``): three launches, no host sync, nothing allocated but the planes asked for in
         ``want`` -- with fixed tables the call can be captured in a HIP graph.  verts0, verts1 (or None) [R, V, 3], cam_t [R, 3], focal [R, 2] fp32,
-        contiguous.  -> the dict of _lib.mesh_render_draws."""
+        contiguous.  -> the dict of _lib.mesh_render_draws; with a third table (``upload_draws(..., grounds=)``) the scene form draws the ground
+        planes in the same launches -> the dict of _lib.mesh_render_scene."""
         if rot is not None and torch.is_tensor(rot):
             if rot.is_cuda:
                 raise RuntimeError('rot is read on the host (it enters the launch as kernel arguments): pass a CPU tensor, numpy array or nested list')
             rot = rot.reshape(3, 3).tolist()
         faces, ptr, idx = self._tables(verts0.device, verts0.shape[1])
+        if len(tables) == 3:
+            return L.mesh_render_scene(verts0, verts1, faces, ptr, idx, cam_t, focal, tables[1], n_draws, tables[0], n_images, total_pixels, tables[2],
+                                       self.color, rot=rot, znear=znear, want=want)
         return L.mesh_render_draws(verts0, verts1, faces, ptr, idx, cam_t, focal, tables[1], n_draws, tables[0], n_images, total_pixels, self.color,
                                    rot=rot, znear=znear, want=want)
 
-    def _run_draws(self, images, table, total, backgrounds, outputs, verts0, verts1, cam_t, focal, rot, znear, want):
-        tables = self.upload_draws(images, table, backgrounds, outputs, verts0.device)
+    def _run_draws(self, images, table, total, backgrounds, outputs, verts0, verts1, cam_t, focal, rot, znear, want, grounds=None):
+        tables = self.upload_draws(images, table, backgrounds, outputs, verts0.device, grounds=grounds)
         return self.run_draws(tables, len(images), len(table), total, verts0, verts1, cam_t, focal, rot=rot, znear=znear, want=want)
 
     def _rows(self, verts, cam_t, focal, what):
@@ -165,14 +244,19 @@ class MeshRenderer:
         return verts, cam_t.float().reshape(P, 3).contiguous(), (focal.expand(P, 2) if focal.shape[1] == 1 else focal).contiguous()
 
     @torch.no_grad()
-    def render_clip(self, frames, verts, cam_t, focal, frame_index, per_person=False, centers=None, rot=None, znear=0.05, want=()):
+    def render_clip(self, frames, verts, cam_t, focal, frame_index, per_person=False, centers=None, rot=None, znear=0.05, want=(), ground=False):
         """The overlays of a clip in ONE call of three launches.  frames: uint8 [F, H, W, 3] on the device or a list of [H_i, W_i, 3] device tensors of
         any sizes and row strides; verts [P, V, 3], cam_t [P, 3], focal [P] or [P, 2]: all persons of the clip; frame_index: the frame of every row
         as HOST integers (list, numpy array, CPU tensor; a device tensor raises RuntimeError: the draw table is packed on the host).  Returns a list
         of F uint8 images [H_i, W_i, 3], all persons of a frame in one depth buffer exactly as ``render`` draws that frame's rows (views of one
         [F, H, W, 3] tensor when the sizes agree; a frame without rows comes back as its own bytes), or with per_person P images, one per row over
         its frame.  centers: (cx, cy) per frame, default (W_i // 2, H_i // 2).  want as for ``render``: a dict with 'image' and lists of per-image
-        planes ('face': the global id draw * F + face with draw = the row; 'screen' [P, V, 3]).  No host sync, no read of device memory."""
+        planes ('face': the global id draw * F + face with draw = the row; 'screen' [P, V, 3]).  ground as for ``render``: a plane under every
+        person (per_person=True or a single row, ValueError otherwise), in the same launches; the dict then has 'ground_y' [P].  No host sync, no
+        read of device memory."""
+        height = _ground_height(ground)
+        if height is not None and not per_person and verts.shape[0] > 1:
+            raise ValueError('a ground plane belongs to one person: %d rows may share an image (per_person=True gives every person an image)' % verts.shape[0])
         if torch.is_tensor(frame_index):
             if frame_index.is_cuda:
                 raise RuntimeError('frame_index is read on the host (the draw table is packed there): pass a list, numpy array or CPU tensor')
@@ -206,44 +290,78 @@ class MeshRenderer:
         draws = [(row, 0, row if per_person else i, 0.0) for row, i in enumerate(index)]
         images, table, total = self.plan_draws(sizes, draws, centers=None if centers is None else [centers[i] for i in targets],
                                                frame_strides=[b.stride(0) for b in backgrounds], n_rows=P)
-        res = self._run_draws(images, table, total, backgrounds, outputs, verts, None, cam_t, focal, rot, znear, want)
+        grounds = None if height is None else self.plan_grounds(len(sizes), draws, [(d[2], row, None if height is True else height) for row, d in enumerate(draws)])
+        res = self._run_draws(images, table, total, backgrounds, outputs, verts, None, cam_t, focal, rot, znear, want, grounds=grounds)
         if not want:
             return outputs
         out = {'image': outputs}
         for k, plane in res.items():
-            out[k] = plane if k == 'screen' else [plane[o:o + h * w].view((h, w) + tuple(plane.shape[1:])) for o, (h, w) in zip(images['pix_off'].tolist(), sizes)]
+            out[k] = plane if k in ('screen', 'ground_y') else [plane[o:o + h * w].view((h, w) + tuple(plane.shape[1:])) for o, (h, w) in zip(images['pix_off'].tolist(), sizes)]
         return out
 
 
-def render_overlay_image(image, camera_translation, vertices, camera_rotation, focal_length, camera_center, renderer, sideview_angle=0):
+def render_overlay_image(image, camera_translation, vertices, camera_rotation, focal_length, camera_center, renderer, sideview_angle=0,
+                         add_ground_plane=False):
     """renderer_cam.py:41-141 for ONE person: image uint8 [H, W, 3] (device), camera_translation [3], vertices [V, 3], focal_length (fx, fy) or a
     [1] / [2] tensor, camera_center (cx, cy); ``renderer`` replaces the faces / mesh_color arguments.  Returns uint8 [H, W, 3]; unlike the reference,
-    camera_translation is not modified in place.  mesh_filename (.obj export) and add_ground_plane are out of scope."""
+    camera_translation is not modified in place.  add_ground_plane: True draws the checkerboard floor at the mesh's lowest point (:95-104), a float
+    at that height; the default is False where the reference's is True, because the callers of this package have never been given a plane and keep
+    their bytes.  mesh_filename is ``export_obj``, a call of its own."""
     if not torch.is_tensor(focal_length):
         focal_length = torch.tensor([float(focal_length[0]), float(focal_length[1])], device=vertices.device)
     return renderer.render(image, vertices.unsqueeze(0), camera_translation.reshape(1, 3), focal_length.reshape(1, -1), center=camera_center,
-                           rot=camera_rotation, sideview_angle=sideview_angle)
+                           rot=camera_rotation, sideview_angle=sideview_angle, ground=add_ground_plane)
 
 
-def render_image_group(image, camera_translation, vertices, local_vertices, camera_rotation, focal_length, camera_center, renderer):
+def render_image_group(image, camera_translation, vertices, local_vertices, camera_rotation, focal_length, camera_center, renderer, ground=False):
     """renderer_cam.py:144-225: the [H, 4 W, 3] uint8 strip  frame | overlay of local_vertices | side view (270 degrees) of local_vertices | side view
-    of vertices,  side views on a black background.  Out of scope: the checkerboard ground plane of the first side view (a PARE helper that is not in
-    the reference tree), the keypoint skeleton, .obj export and cv2.imwrite -- the tensor is returned and the caller saves it."""
+    of vertices,  side views on a black background.  ground=True puts the checkerboard floor of the reference under BOTH side views, each at the
+    lowest point of its own mesh (the overlay never has one, :185): against the level floor the camera-frame mesh leans by the camera's pitch and
+    roll and the world-frame mesh stands upright.  Out of scope: the keypoint skeleton and cv2.imwrite -- the tensor is returned and the caller
+    saves it; ``export_obj`` writes the meshes."""
     over = render_overlay_image(image, camera_translation, local_vertices, camera_rotation, focal_length, camera_center, renderer)
     black = torch.zeros_like(image)
-    side0 = render_overlay_image(black, camera_translation, local_vertices, camera_rotation, focal_length, camera_center, renderer, sideview_angle=270)
-    side1 = render_overlay_image(black, camera_translation, vertices, camera_rotation, focal_length, camera_center, renderer, sideview_angle=270)
+    side0 = render_overlay_image(black, camera_translation, local_vertices, camera_rotation, focal_length, camera_center, renderer, sideview_angle=270,
+                                 add_ground_plane=ground)
+    side1 = render_overlay_image(black, camera_translation, vertices, camera_rotation, focal_length, camera_center, renderer, sideview_angle=270,
+                                 add_ground_plane=ground)
     return torch.cat([image, over, side0, side1], dim=1)
 
 
+def export_obj(path, vertices, faces, sideview_angle=0, camera_translation=None):
+    """The mesh as the reference exports it behind --save_obj (renderer_cam.py:73-87: ``mesh.export(mesh_filename)`` after the 180 degree turn about X
+    and, for sideview_angle > 0, the turn about Y): ``v x y z`` lines (%.9g of the float32 coordinates, which reads back exactly) and 1-based
+    ``f i j k`` lines -- trimesh's own text is unpinned, the file is defined here.  If ``path`` does not end in ``_rot.obj``, path[:-4] + '.npy'
+    gets the camera translation t' = (-t_x, t_y, t_z) (:84-87).  vertices [V, 3] and camera_translation [3] may be device tensors: each is copied
+    to the host once."""
+    v = (vertices.detach().cpu().numpy() if torch.is_tensor(vertices) else np.asarray(vertices)).astype(np.float64).reshape(-1, 3)
+    f = (faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)).astype(np.int64).reshape(-1, 3)
+    v = v * np.array([1.0, -1.0, -1.0])                                               # D
+    if sideview_angle > 0:
+        a = math.radians(float(sideview_angle))
+        v = v @ np.array([[math.cos(a), 0.0, math.sin(a)], [0.0, 1.0, 0.0], [-math.sin(a), 0.0, math.cos(a)]]).T       # S
+    v = v.astype(np.float32)
+    with open(path, 'w') as out:
+        out.write(''.join('v %.9g %.9g %.9g\n' % (x, y, z) for x, y, z in v.tolist()))
+        out.write(''.join('f %d %d %d\n' % (i + 1, j + 1, k + 1) for i, j, k in f.tolist()))
+    if not str(path).endswith('_rot.obj'):
+        if camera_translation is None:
+            raise ValueError('%s: the camera translation is saved beside every mesh that is not a _rot.obj' % path)
+        t = camera_translation.detach().cpu().numpy() if torch.is_tensor(camera_translation) else np.asarray(camera_translation)
+        np.save(str(path)[:-4] + '.npy', t.reshape(3) * np.array([-1, 1, 1], dtype=t.dtype))
+
+
 @torch.no_grad()
-def render_clip_groups(frames, camera_translation, vertices, local_vertices, camera_rotation, focal_length, frame_index, renderer, camera_centers=None):
+def render_clip_groups(frames, camera_translation, vertices, local_vertices, camera_rotation, focal_length, frame_index, renderer, camera_centers=None,
+                       ground=False):
     """``render_image_group`` for every person of a clip in ONE call of three launches.  frames: uint8 [F, H, W, 3] or a list of [H_i, W_i, 3] device
     tensors; camera_translation [P, 3], vertices / local_vertices [P, V, 3], focal_length [P] or [P, 2]: all persons of the clip; frame_index: the
     frame of every person as HOST integers; camera_rotation: 3 x 3 HOST values or None; camera_centers: (cx, cy) per frame, default the frame centre.
     Returns P strips uint8 [H_i, 4 W_i, 3] (views of one [P, H, 4 W, 3] tensor when the sizes agree), equal to render_image_group per person: the
     frame is copied into panel 0 and the three draws of a person (local at 0 degrees over the frame, local and vertices at 270 degrees on black) are
-    written straight into panels 1 to 3 through the output row stride."""
+    written straight into panels 1 to 3 through the output row stride.  ground as for ``render_image_group``: the floor under panels 2 and 3, each
+    at its own mesh's lowest point (or at a float height), in the same launch group."""
+    height = _ground_height(ground)
     if torch.is_tensor(frame_index):
         if frame_index.is_cuda:
             raise RuntimeError('frame_index is read on the host (the draw table is packed there): pass a list, numpy array or CPU tensor')
@@ -277,5 +395,9 @@ def render_clip_groups(frames, camera_translation, vertices, local_vertices, cam
             outputs.append(strips[p][:, panel * w:(panel + 1) * w])
     images, table, total = renderer.plan_draws(sizes, draws, centers=centers, frame_strides=[frame_list[i].stride(0) for i in index for _ in range(4)],
                                                out_strides=[o.stride(0) for o in outputs], have_verts1=True, n_rows=P)
-    renderer._run_draws(images, table, total, backgrounds, outputs, local, world, cam_t, focal, camera_rotation, 0.05, ())
+    grounds = None
+    if height is not None:                                                                          # person p: images 4 p + 2, 4 p + 3 are drawn by draws 3 p + 1, 3 p + 2
+        y = None if height is True else height
+        grounds = renderer.plan_grounds(len(sizes), draws, [(4 * p + k + 1, 3 * p + k, y) for p in range(P) for k in (1, 2)])
+    renderer._run_draws(images, table, total, backgrounds, outputs, local, world, cam_t, focal, camera_rotation, 0.05, (), grounds=grounds)
     return strips
