@@ -812,6 +812,21 @@ struct whmr_augment_item {
 };
 int whmr_augment_crop(const void* items, int B, int max_box_w, int max_box_h, int any_rot, void* rot_scratch, void* mid_scratch,
                       int32_t* coef_scratch, float* out, uint8_t* raw, const float* mean3, const float* std3, void* stream);
+/* The same with synthetic occluders (USE_SYNTHETIC_OCCLUSION, base_dataset.py:192-194) pasted between the flip and the colour noise, inside the
+ * vertical-pass launch (still four launches).  bank: DEVICE bytes, RGBA objects [h, w, 4] uint8 back to back, 4-byte aligned; bank_table: DEVICE
+ * [n_objects, 3] int64 = (byte offset into bank, h, w) per object, 1 <= h, w <= 32767 and 255 h w < 2^31; pastes: DEVICE [n_pastes, 5] int32 =
+ * (object, nw, nh, start_x, start_y): the object resized to nw x nh (1 <= nw <= w, 1 <= nh <= h) covers [start, start + (nw, nh)) of the 256 x 256
+ * patch, rows in paste order; paste_ptr: DEVICE [B + 1] int32, sample b owns rows [paste_ptr[b], paste_ptr[b + 1]) -- read clamped to
+ * [0, n_pastes], so rows that do not start at 0 or run past the array reach no memory outside it.  The resize is an area average DEFINED in
+ * integers: along an axis of source length S resized to n, output u covers [u S, (u + 1) S) and texel j covers [j n, (j + 1) n) in units of 1 / n
+ * texel, the weight is the integer overlap, and a channel (alpha included) is (2 sum(wy wx v) + w h) // (2 w h).  Blend: a = fp32(A) / 255,
+ * dst = uint8(a src + (1 - a) dst) in fp32, truncated; the next paste sees it.  A row naming an object outside the table, an object not wholly
+ * inside bank, or nw / nh outside its range is skipped on the device.  n_pastes = 0 runs whmr_augment_crop's kernels.  hipErrorInvalidValue: a
+ * negative n_pastes, n_objects or bank_bytes; with n_pastes > 0 a null or misaligned bank, a null table, pastes or paste_ptr, or n_objects = 0. */
+int whmr_augment_crop_occluded(const void* items, int B, int max_box_w, int max_box_h, int any_rot, void* rot_scratch, void* mid_scratch,
+                               int32_t* coef_scratch, float* out, uint8_t* raw, const float* mean3, const float* std3, const uint8_t* bank,
+                               int64_t bank_bytes, const int64_t* bank_table, int n_objects, const int32_t* pastes, const int32_t* paste_ptr,
+                               int n_pastes, void* stream);
 /* Labels of the same batch: one workgroup per sample, float64.  io (HOST struct of DEVICE pointers): the resident annotation arrays (float64;
  * S and smpl_2dkps nullable = absent from the dataset), mask [B, 431] bytes, and one output per key of the batch dictionary. */
 struct whmr_augment_labels_io {

@@ -303,6 +303,7 @@ _SIGS = {
     'whmr_adam_guard_advance': [_P, _I, _P, _P, _I, _P, _P, _P],
     'whmr_adam_step_guarded': [_P, _I, _I, _P, _P, _P],
     'whmr_augment_crop': [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    'whmr_augment_crop_occluded': [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _I, _P, _P, _I, _P],
     'whmr_augment_labels': [_P, _I, C.POINTER(_WhmrAugmentLabelsIO), _P],
     'whmr_maxpool_nhwc': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'whmr_avgpool_nhwc': [_P, _P, _I, _I, _I, _I, _P],
@@ -1753,6 +1754,21 @@ def augment_crop(items, B, max_box_w, max_box_h, any_rot, rot_scratch, mid_scrat
     m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     _check(lib().whmr_augment_crop(items.data_ptr(), B, max_box_w, max_box_h, int(any_rot), _ptr(rot_scratch), mid_scratch.data_ptr(),
                                    coef_scratch.data_ptr(), out.data_ptr(), _ptr(raw), m3, s3, _stream()), 'whmr_augment_crop')
+    return out
+
+
+def augment_crop_occluded(items, B, max_box_w, max_box_h, any_rot, rot_scratch, mid_scratch, coef_scratch, out, raw, mean, std, bank, bank_table,
+                          pastes_ptr, paste_ptr_ptr, n_pastes):
+    """augment_crop with the occluder stage (whmr_augment_crop_occluded); bank uint8 [bytes] and bank_table int64 [n, 3]: an OccluderBank's resident
+    tensors; pastes_ptr / paste_ptr_ptr: device addresses of the int32 [n_pastes, 5] rows and the [B + 1] row pointers inside the uploaded table"""
+    _dev(items, rot_scratch, mid_scratch, coef_scratch, out, raw, bank, bank_table)
+    assert out.dtype == torch.float32 and out.is_contiguous() and coef_scratch.dtype == torch.int32
+    assert bank.dtype == torch.uint8 and bank.is_contiguous() and bank_table.dtype == torch.int64 and bank_table.is_contiguous() and bank_table.shape[1:] == (3,)
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    _check(lib().whmr_augment_crop_occluded(items.data_ptr(), B, max_box_w, max_box_h, int(any_rot), _ptr(rot_scratch), mid_scratch.data_ptr(),
+                                            coef_scratch.data_ptr(), out.data_ptr(), _ptr(raw), m3, s3, bank.data_ptr(), bank.numel(),
+                                            bank_table.data_ptr(), bank_table.shape[0], pastes_ptr, paste_ptr_ptr, int(n_pastes), _stream()),
+           'whmr_augment_crop_occluded')
     return out
 
 

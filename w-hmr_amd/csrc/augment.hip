@@ -7,10 +7,17 @@
 //   3. resize to 256 x 256 with Pillow's antialiased bicubic (a = -0.5, support 2 max(1, box / 256)) in its 8-bit integer arithmetic: taps
 //      computed in float64 exactly as precompute_coeffs does (no fused multiply-add: see the pragma), normalised, rounded to 22 fractional bits,
 //      accumulator started at one half, shifted, clipped -- horizontal pass, then vertical pass           [3P Pillow ImagingResample, restated]
-//   4. mirror in x when flip;  5. min(255, max(0, v pn[c])) truncated to uint8, / 255, - mean, / std, NCHW fp32.
+//   4. mirror in x when flip;
+//   4a. occluders (whmr_augment_crop_occluded only; USE_SYNTHETIC_OCCLUSION, base_dataset.py:192-194): up to 7 pastes per sample, in order; each
+//      resizes an RGBA object [h, w, 4] of the resident bank to (nw, nh) by area averaging and blends it over the patch at [start, start + (nw, nh)):
+//      a = fp32(A) / 255, dst = uint8(a src + (1 - a) dst) in fp32, truncated.  The resize is DEFINED in integers: along an axis of source length S
+//      and resized length n, output u covers [u S, (u + 1) S) and source texel j covers [j n, (j + 1) n) in units of 1 / n texel; the weight is the
+//      integer overlap (weights of an axis sum to S); a channel is (2 sum(wy wx v) + D) // (2 D), D = w h (round half up), alpha included.  Within
+//      0.5 of the float64 area average, the identity at n == S.             [3P PARE occlude_with_pascal_objects over cv2 INTER_AREA: parity unpinned]
+//   5. min(255, max(0, v pn[c])) truncated to uint8, / 255, - mean, / std, NCHW fp32.
 //   Only the 192 columns the model reads (32 .. 223 of 256) go through either pass.
 //   Four launches: taps (B x 2 x 256 threads), rotation (rot != 0 samples), horizontal pass -> [box_h, 192, 3] uint8 scratch, vertical pass +
-//   stages 4 / 5.  The intermediate lives in a global scratch, not in LDS: a box is up to thousands of rows high and its 192 x 3 bytes per row
+//   stages 4 / 4a / 5 (4a: a second instantiation of the vertical-pass kernel, no extra launch and no extra pass over the patch).  The intermediate lives in a global scratch, not in LDS: a box is up to thousands of rows high and its 192 x 3 bytes per row
 //   are read ~2 support / scale = 4 times by the vertical pass from L2; an LDS tile would have to re-run the horizontal pass on the overlap rows.
 //
 // whmr_augment_labels = j2d_processing / j3d_processing / pose_processing / keypoints_world / bbox_info (base_dataset.py:209-247,294-373) with
@@ -152,10 +159,63 @@ __global__ __launch_bounds__(256) void augment_hpass_kernel(const whmr_augment_i
     o[0] = (uint8_t)clip8(acc[0]); o[1] = (uint8_t)clip8(acc[1]); o[2] = (uint8_t)clip8(acc[2]);
 }
 
-// stage 3, vertical + stages 4, 5
+// stage 4a: the occluder bank (RGBA texels, objects back to back), its table of (byte offset, h, w) per object, the paste rows
+// (object, nw, nh, start_x, start_y) of the whole batch and the [B + 1] row pointers into them
+struct occluder_args {
+    const uint8_t* bank; int64_t bank_bytes;
+    const int64_t* table; int n_objects;
+    const int32_t* pastes; const int32_t* paste_ptr; int n_pastes;
+};
+#define OCC_MAX_SIDE 32767          // u * w and j * n stay below 2^30
+
+// the pastes of sample b over pixel (x, y) of the 256 x 256 patch, in order; rows [wg_y0, wg_y1] are those of the calling workgroup.  Everything up
+// to the rectangle test depends on blockIdx only: the loop's trip count and its early exits are workgroup-uniform, the rows are scalar loads.
+__device__ __forceinline__ void occlude_pixel(const occluder_args& oc, int b, int x, int y, int wg_y0, int wg_y1, int px[3]) {
+    const int p0 = max(oc.paste_ptr[b], 0), p1 = min(oc.paste_ptr[b + 1], oc.n_pastes);         // never a row outside the paste array
+    for (int p = p0; p < p1; ++p) {
+        const int32_t* ps = oc.pastes + (int64_t)p * 5;
+        const int oi = ps[0], nw = ps[1], nh = ps[2], sx = ps[3], sy = ps[4];
+        if (nw <= 0 || nh <= 0 || sy > wg_y1 || (int64_t)sy + nh <= wg_y0 || (unsigned)oi >= (unsigned)oc.n_objects) continue;
+        const int64_t off = oc.table[3 * (int64_t)oi], h64 = oc.table[3 * (int64_t)oi + 1], w64 = oc.table[3 * (int64_t)oi + 2];
+        if (off < 0 || (off & 3) || h64 < 1 || w64 < 1 || h64 > OCC_MAX_SIDE || w64 > OCC_MAX_SIDE || nw > w64 || nh > h64
+            || h64 * w64 * 255 >= ((int64_t)1 << 31) || off + h64 * w64 * 4 > oc.bank_bytes) continue;                                  // an object that is not wholly inside the bank is not read
+        const int h = (int)h64, w = (int)w64;
+        const int64_t u64 = (int64_t)x - sx, v64 = (int64_t)y - sy;
+        if (u64 < 0 || u64 >= nw || v64 < 0 || v64 >= nh) continue;                            // per lane from here on
+        const int u = (int)u64, v = (int)v64;
+        const uint32_t* tex = (const uint32_t*)(oc.bank + off);                                // one texel = R | G << 8 | B << 16 | A << 24
+        const int ux0 = u * w, ux1 = ux0 + w, vy0 = v * h, vy1 = vy0 + h;                      // the output texel's extent in 1 / nw, 1 / nh texels
+        const int jx0 = ux0 / nw, jx1 = min((ux1 - 1) / nw, w - 1), jy0 = vy0 / nh, jy1 = min((vy1 - 1) / nh, h - 1);
+        uint32_t sum[4] = {0u, 0u, 0u, 0u};                                                     // <= 255 w h < 2^31 (the host rejects larger objects)
+        for (int jy = jy0; jy <= jy1; ++jy) {
+            const uint32_t wy = (uint32_t)(min((jy + 1) * nh, vy1) - max(jy * nh, vy0));
+            const uint32_t* line = tex + (int64_t)jy * w;
+            uint32_t r[4] = {0u, 0u, 0u, 0u};
+            for (int jx = jx0; jx <= jx1; ++jx) {
+                const uint32_t wx = (uint32_t)(min((jx + 1) * nw, ux1) - max(jx * nw, ux0));
+                const uint32_t t = line[jx];
+                r[0] += wx * (t & 255u); r[1] += wx * ((t >> 8) & 255u); r[2] += wx * ((t >> 16) & 255u); r[3] += wx * (t >> 24);
+            }
+            sum[0] += wy * r[0]; sum[1] += wy * r[1]; sum[2] += wy * r[2]; sum[3] += wy * r[3];
+        }
+        const uint32_t D = (uint32_t)w * (uint32_t)h;
+        uint32_t val[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {                                                           // (2 sum + D) // (2 D) without leaving 32 bits
+            const uint32_t q = sum[c] / D, rem = sum[c] - q * D;
+            val[c] = q + (2u * rem >= D ? 1u : 0u);
+        }
+        const float a = __fdiv_rn((float)val[3], 255.0f), na = 1.0f - a;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c] = (int)(a * (float)val[c] + na * (float)px[c]);      // truncation into the uint8 patch
+    }
+}
+
+// stage 3, vertical + stages 4, 5 (OCC: + stage 4a between them; the instantiation without it is the kernel of whmr_augment_crop)
+template <bool OCC>
 __global__ __launch_bounds__(256) void augment_vpass_kernel(const whmr_augment_item* __restrict__ items, const int32_t* __restrict__ coef,
                                                             const uint8_t* __restrict__ mid, float* __restrict__ out, uint8_t* __restrict__ raw,
-                                                            float m0, float m1, float m2, float s0, float s1, float s2) {
+                                                            float m0, float m1, float m2, float s0, float s1, float s2, occluder_args oc) {
     const int b = blockIdx.y;
     const whmr_augment_item& it = items[b];
     const int idx = blockIdx.x * 256 + threadIdx.x;              // grid.x = 256 * 192 / 256
@@ -169,18 +229,21 @@ __global__ __launch_bounds__(256) void augment_vpass_kernel(const whmr_augment_i
         const int w = row[2 + k];
         acc[0] += w * p[0]; acc[1] += w * p[1]; acc[2] += w * p[2];
     }
+    int px[3] = {clip8(acc[0]), clip8(acc[1]), clip8(acc[2])};
+    if constexpr (OCC) occlude_pixel(oc, b, X0 + j, yy, (int)(blockIdx.x * 256) / OUT_W, (int)(blockIdx.x * 256 + 255) / OUT_W, px);
     const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const double noisy = fmin(255.0, fmax(0.0, (double)clip8(acc[c]) * it.pn[c]));
+        const double noisy = fmin(255.0, fmax(0.0, (double)px[c] * it.pn[c]));
         const int v = (int)noisy;                                 // the float product goes back into a uint8 array (base_dataset.py:202-204)
         out[(((int64_t)b * 3 + c) * RES + yy) * OUT_W + j] = __fdiv_rn(__fdiv_rn((float)v, 255.0f) - mean[c], sd[c]);
         if (raw) raw[(((int64_t)b * RES + yy) * OUT_W + j) * 3 + c] = (uint8_t)v;
     }
 }
 
-extern "C" int whmr_augment_crop(const void* items, int B, int max_box_w, int max_box_h, int any_rot, void* rot_scratch, void* mid_scratch,
-                                 int32_t* coef_scratch, float* out, uint8_t* raw, const float* mean3, const float* std3, void* stream) {
+static int augment_crop_launch(const void* items, int B, int max_box_w, int max_box_h, int any_rot, void* rot_scratch, void* mid_scratch,
+                               int32_t* coef_scratch, float* out, uint8_t* raw, const float* mean3, const float* std3, const occluder_args* oc,
+                               void* stream) {
     if (B <= 0 || max_box_w <= 0 || max_box_h <= 0) return (int)hipErrorInvalidValue;
     const whmr_augment_item* it = (const whmr_augment_item*)items;
     hipStream_t s = (hipStream_t)stream;
@@ -194,10 +257,30 @@ extern "C" int whmr_augment_crop(const void* items, int B, int max_box_w, int ma
     hipLaunchKernelGGL(augment_hpass_kernel, dim3((unsigned)(((int64_t)max_box_h * OUT_W + 255) / 256), B), dim3(256), 0, s, it, coef_scratch,
                        (const uint8_t*)rot_scratch, (uint8_t*)mid_scratch);
     WHMR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(augment_vpass_kernel, dim3(RES * OUT_W / 256, B), dim3(256), 0, s, it, coef_scratch, (const uint8_t*)mid_scratch, out, raw,
-                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    if (oc)
+        hipLaunchKernelGGL(augment_vpass_kernel<true>, dim3(RES * OUT_W / 256, B), dim3(256), 0, s, it, coef_scratch, (const uint8_t*)mid_scratch, out,
+                           raw, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], *oc);
+    else
+        hipLaunchKernelGGL(augment_vpass_kernel<false>, dim3(RES * OUT_W / 256, B), dim3(256), 0, s, it, coef_scratch, (const uint8_t*)mid_scratch, out,
+                           raw, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], occluder_args{});
     WHMR_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int whmr_augment_crop(const void* items, int B, int max_box_w, int max_box_h, int any_rot, void* rot_scratch, void* mid_scratch,
+                                 int32_t* coef_scratch, float* out, uint8_t* raw, const float* mean3, const float* std3, void* stream) {
+    return augment_crop_launch(items, B, max_box_w, max_box_h, any_rot, rot_scratch, mid_scratch, coef_scratch, out, raw, mean3, std3, nullptr, stream);
+}
+
+extern "C" int whmr_augment_crop_occluded(const void* items, int B, int max_box_w, int max_box_h, int any_rot, void* rot_scratch, void* mid_scratch,
+                                          int32_t* coef_scratch, float* out, uint8_t* raw, const float* mean3, const float* std3,
+                                          const uint8_t* bank, int64_t bank_bytes, const int64_t* bank_table, int n_objects, const int32_t* pastes,
+                                          const int32_t* paste_ptr, int n_pastes, void* stream) {
+    if (n_pastes < 0 || n_objects < 0 || bank_bytes < 0) return (int)hipErrorInvalidValue;
+    if (n_pastes > 0 && (!bank || ((uintptr_t)bank & 3) || bank_bytes < 4 || !bank_table || n_objects < 1 || !pastes || !paste_ptr)) return (int)hipErrorInvalidValue;
+    const occluder_args oc = {bank, bank_bytes, bank_table, n_objects, pastes, paste_ptr, n_pastes};
+    return augment_crop_launch(items, B, max_box_w, max_box_h, any_rot, rot_scratch, mid_scratch, coef_scratch, out, raw, mean3, std3,
+                               n_pastes > 0 ? &oc : nullptr, stream);
 }
 
 // ----------------------------------------------------------------------------- labels

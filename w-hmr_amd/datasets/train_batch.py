@@ -5,14 +5,29 @@ The reference makes every sample on the CPU: it draws the augmentation (``augm_p
 resizes it with Pillow, flips it, scales the colour channels, normalises, and pushes keypoints, 3-D joints and the SMPL pose through the same flip /
 rotation / scale.  Here the annotation arrays are uploaded once (``TrainBatchMaker``), and per batch the host computes -- in float64 numpy, exactly as
 the reference does -- only the per-sample geometry (box corners and pad with their ``int`` truncations, the 3 x 3 ``get_transform`` matrix, the
-rotation's inverse map) and uploads it as ONE table (struct whmr_augment_item, include/whmr_hip.h) that also names every source image by pointer,
+rotation's inverse map, the occluders' rectangles) and uploads it as ONE table (struct whmr_augment_item, include/whmr_hip.h) that also names every source image by pointer,
 size and row stride.  Everything per pixel and per label runs in csrc/augment.hip (five launches, no host synchronisation).
 
-Out of scope (the image differs from the reference's where these are switched on): the synthetic occluders (``USE_SYNTHETIC_OCCLUSION``: needs the
-Pascal VOC objects), the albumentations ``ColorJitter`` (p = 0.2; its arithmetic and random order are not pinned here) and ``agora_crop``'s special
-case (no crop).  A sample whose crop raises in the reference (base_dataset.py:282-287 then retries with the unscaled box) raises here.
+Stages of the image: 1. integer box, 2. rotation, 3. Pillow's bicubic resize, 4. flip, 4a. occluders, 5. colour noise + normalise (csrc/augment.hip).
+
+4a. occluders (``USE_SYNTHETIC_OCCLUSION``, on by default in the reference: base_dataset.py:192-194 pastes Pascal VOC objects onto every training
+sample with PARE's ``occlude_with_pascal_objects``): give ``TrainBatchMaker`` the list of RGBA objects PARE's ``load_pascal_occluders`` (or its
+cached pickle) yields.  They are packed once into a resident ``OccluderBank``; per batch ``draw_occlusions`` draws, per sample, 1 .. 7 pastes of
+(object, factor in [0.2, 1], centre in the 256 x 256 patch), the host turns each into an integer rectangle in float64 as numpy does (sizes
+``np.round((w, h) * factor)``, ``start = np.round(centre) - size // 2``) and the rows travel in the call's one upload.  The device resizes the
+object by AREA AVERAGING and alpha-blends it (``a = fp32(A) / 255; dst = uint8(a src + (1 - a) dst)``) inside the vertical-pass launch.  The
+resize is defined here in integers so that host and device agree to the bit: along an axis of source length S resized to n, output u covers
+[u S, (u + 1) S) and source texel j covers [j n, (j + 1) n) in units of 1 / n texel; the weight is the integer overlap (the weights of an axis sum
+to S); a resized channel, alpha included, is ``(2 sum(wy wx v) + D) // (2 D)`` with D = w h (round half up).  That is within 0.5 of the float64
+area average (at most one grey level from cv2's INTER_AREA at ties), the identity at n == S and the rounded block mean at integer ratios.  PARE and
+cv2 are not available where this was written: parity with PARE / cv2 is unpinned (as skimage's rotation is).
+
+Out of scope (the image differs from the reference's where these are switched on): the albumentations ``ColorJitter`` (p = 0.2; its arithmetic and
+random order are not pinned here), ``agora_crop``'s special case (no crop) and reading the occluders out of a Pascal VOC tree (cv2 morphology).
+A sample whose crop raises in the reference (base_dataset.py:282-287 then retries with the unscaled box) raises here.
 Image decoding stays with the caller.
 """
+import random
 import struct
 
 import numpy as np
@@ -52,6 +67,75 @@ def draw_meta_mask(n, rng=np.random, is_train=True, percent=0.3):
             masked = int(rng.random_sample() * percent * N_MASK)
             mask[i, rng.choice(np.arange(N_MASK), replace=False, size=masked)] = 0
     return mask
+
+
+def draw_occlusions(n, n_occluders, rng=np.random, pyrng=random):
+    """the draws of ``occlude_with_pascal_objects`` for n samples -> list of n float64 arrays [k_i, 4] = (occluder index, factor, cx, cy).  Per sample
+    ``count = rng.randint(1, 8)``, then per paste ``random.choice(occluders)`` (Python's generator: ``pyrng.randrange`` consumes the same stream),
+    ``rng.uniform(0.2, 1.0)`` and ``rng.uniform([0, 0], [256, 256])``, in this order: the same seeds give the same numbers."""
+    out = []
+    for _ in range(n):
+        rows = np.zeros((rng.randint(1, 8), 4))
+        for row in rows:
+            row[0] = pyrng.randrange(n_occluders)
+            row[1] = rng.uniform(0.2, 1.0)
+            row[2:] = rng.uniform([0, 0], [RES, RES])
+        out.append(rows)
+    return out
+
+
+def plan_occlusions(occlusions, sizes):
+    """occlusions: per sample [k, 4] (occluder index, factor, cx, cy) as ``draw_occlusions`` returns them; sizes: int [n_occluders, 2] = (h, w).
+    -> (pastes int32 [n_pastes, 5] = (index, nw, nh, start_x, start_y), row pointers int32 [B + 1]), in float64 / int arithmetic as the reference
+    runs it: ``(nw, nh) = np.round((w, h) * factor).astype(int)`` (half to even), ``start = np.round(centre).astype(int32) - (nw, nh) // 2``.
+    Dropped: a paste with nw == 0 or nh == 0 (the reference raises inside cv2 and retries the whole sample), and one whose rectangle misses the
+    kept columns 32 .. 223 or the rows 0 .. 255.  An index outside the bank raises ValueError."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    occ = [np.asarray(o, dtype=np.float64).reshape(-1, 4) for o in occlusions]
+    allp = np.concatenate(occ + [np.zeros((0, 4))])                # one vectorised pass over the pastes of the batch
+    k, factor = allp[:, 0], allp[:, 1]
+    if not np.isfinite(allp).all():
+        raise ValueError('occlusions hold a non-finite number')
+    if not ((k == np.floor(k)) & (k >= 0) & (k < len(sizes))).all():
+        raise ValueError('occluder index outside the bank of %d: %r' % (len(sizes), k[~((k == np.floor(k)) & (k >= 0) & (k < len(sizes)))][:4]))
+    if not ((factor >= 0.0) & (factor <= 1.0)).all():
+        raise ValueError('occluder factor outside [0, 1] (the resize only shrinks)')
+    k = k.astype(np.int64)
+    n = np.round(sizes[k][:, ::-1] * factor[:, None]).astype(int)                         # (nw, nh)
+    start = np.round(allp[:, 2:]).astype(np.int32) - n // 2
+    keep = ((n > 0).all(1) & (start[:, 0] + n[:, 0] > X_SLICE[0]) & (start[:, 0] < X_SLICE[1]) & (start[:, 1] + n[:, 1] > 0) & (start[:, 1] < RES))
+    sample = np.repeat(np.arange(len(occ)), [len(o) for o in occ])
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(sample[keep], minlength=len(occ)))])
+    rows = np.concatenate([k[:, None], n, start], axis=1)[keep]
+    return np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 5), ptr.astype(np.int32)
+
+
+class OccluderBank:
+    """occluders: list of uint8 [h, w, 4] RGBA arrays (what PARE's ``load_pascal_occluders`` yields), packed once into one byte buffer on ``device``
+    (``bank``) plus an int64 table [n, 3] of (byte offset, h, w) per object (``table``); ``sizes`` [n, 2] = (h, w) stays on the host for the
+    per-batch plan.  ValueError: an empty list, anything that is not uint8 [h, w, 4] with h, w >= 1, a side above 32767 or 255 h w >= 2^31 (the
+    device sums a resized texel in 32 bits)."""
+
+    def __init__(self, occluders, device):
+        occluders = list(occluders)
+        if not occluders:
+            raise ValueError('OccluderBank needs at least one occluder')
+        table, off = [], 0
+        for i, o in enumerate(occluders):
+            if not (isinstance(o, np.ndarray) and o.dtype == np.uint8 and o.ndim == 3 and o.shape[2] == 4 and o.shape[0] >= 1 and o.shape[1] >= 1):
+                raise ValueError('occluder %d is not a uint8 [h, w, 4] RGBA array with h, w >= 1' % i)
+            h, w = o.shape[:2]
+            if max(h, w) > 32767 or 255 * h * w >= 2 ** 31:
+                raise ValueError('occluder %d (%d x %d) is too large for the 32-bit area sum' % (i, h, w))
+            table.append((off, h, w))
+            off += h * w * 4
+        self.device = torch.device(device)
+        self.sizes = np.array([t[1:] for t in table], dtype=np.int64)
+        self.bank = torch.from_numpy(np.concatenate([np.ascontiguousarray(o).reshape(-1) for o in occluders])).to(self.device)
+        self.table = torch.tensor(table, dtype=torch.int64).to(self.device)
+
+    def __len__(self):
+        return len(self.sizes)
 
 
 def _get_transform(center, scale, rot):
@@ -96,13 +180,19 @@ def _f64(a, shape):
 class TrainBatchMaker:
     """labels: dict of the dataset's annotation arrays -- ``center`` [N, 2], ``scale`` [N], and optionally ``pose`` [N, 72] + ``shape`` [N, 10]
     (+ ``has_smpl`` [N]), ``part`` [N, 24, 3], ``openpose`` [N, 25, 3], ``S`` [N, 24, 4], ``smpl_2dkps`` [N, 24, 3], ``gender`` [N] ('m' / other);
-    missing ones default as base_dataset.py:74-130 does.  They are uploaded once (float64) and stay on ``device``."""
+    missing ones default as base_dataset.py:74-130 does.  They are uploaded once (float64) and stay on ``device``.  occluders: None, a list of uint8
+    [h, w, 4] RGBA objects or an ``OccluderBank`` on ``device``: switches stage 4a (synthetic occlusion) on for training batches."""
 
-    def __init__(self, labels, device, rot_factor=30, noise_factor=0.4, scale_factor=0.25, is_train=True, ignore_3d=False):
+    def __init__(self, labels, device, rot_factor=30, noise_factor=0.4, scale_factor=0.25, is_train=True, ignore_3d=False, occluders=None):
         device = torch.device(device)
         if device.type != 'cuda':
             raise RuntimeError('TrainBatchMaker runs on a HIP device only (no CPU fallback)')
         self.device, self.is_train = device, is_train
+        self.bank = None
+        if occluders is not None:
+            self.bank = occluders if isinstance(occluders, OccluderBank) else OccluderBank(occluders, device)
+            if self.bank.bank.device != torch.empty(0, device=device).device:
+                raise ValueError('the OccluderBank lives on %s, the maker on %s' % (self.bank.bank.device, device))
         self.factors = dict(rot_factor=rot_factor, noise_factor=noise_factor, scale_factor=scale_factor)
         self.center = _f64(labels['center'], (2,))
         self.scale = np.asarray(labels['scale'], dtype=np.float64).reshape(-1)
@@ -125,13 +215,27 @@ class TrainBatchMaker:
         gender = np.array([0 if str(g) == 'm' else 1 for g in labels['gender']]) if 'gender' in labels else -np.ones(n)
         self.gender = up(np.ascontiguousarray(gender.astype(np.int32)))
 
+    def _occlusion_plan(self, occlusions, B):
+        """the paste rows and row pointers of one call (``plan_occlusions``); occlusions None: drawn when the maker has a bank and is_train"""
+        if occlusions is None:
+            if self.bank is None or not self.is_train:
+                return np.zeros((0, 5), dtype=np.int32), np.zeros(B + 1, dtype=np.int32)
+            occlusions = draw_occlusions(B, len(self.bank))
+        elif self.bank is None:
+            raise ValueError('occlusions= given to a TrainBatchMaker without occluders')
+        if len(occlusions) != B:
+            raise ValueError('occlusions has %d entries for a batch of %d' % (len(occlusions), B))
+        return plan_occlusions(occlusions, self.bank.sizes)
+
     @torch.no_grad()
-    def __call__(self, images, sample_index, params=None, kp_is_smpl=False, meta_mask=None, want_raw=False):
+    def __call__(self, images, sample_index, params=None, kp_is_smpl=False, meta_mask=None, want_raw=False, occlusions=None):
         """images: list of B uint8 [H_i, W_i, 3] RGB tensors on the device (numpy arrays are uploaded, once each; sizes may differ);
         sample_index: B indices into the annotation arrays; params: (flip, pn, rot, sc) as ``draw_augm_params`` returns them (None: drawn here,
         which also draws meta_mask unless given); kp_is_smpl: the 'surreal' joint convention of flip_kp.
         -> dict of device tensors with the keys and dtypes of ``__getitem__`` stacked over the batch; ``img`` is [B, 3, 256, 192] (columns 32 .. 223
-        computed directly).  want_raw adds ``img_u8`` [B, 256, 192, 3], the patch before ``/ 255``."""
+        computed directly).  want_raw adds ``img_u8`` [B, 256, 192, 3], the patch before ``/ 255`` (occluded, after pn).
+        occlusions: list of B arrays [k, 4] = (occluder index, factor, cx, cy) as ``draw_occlusions`` returns them, always applied (ValueError
+        without a bank); None: drawn when the maker has occluders and is_train, between the draws of params and of meta_mask."""
         dev = self.device
         imgs = []
         for im in images:
@@ -146,6 +250,7 @@ class TrainBatchMaker:
         assert len(imgs) == B and B > 0 and index.min() >= 0 and index.max() < self.n
         if params is None:
             params = draw_augm_params(B, is_train=self.is_train, **self.factors)
+        pastes, paste_ptr = self._occlusion_plan(occlusions, B)
         if meta_mask is None:
             meta_mask = draw_meta_mask(B, is_train=self.is_train)
         flip, pn, rot, sc = (np.asarray(p) for p in params)
@@ -179,13 +284,22 @@ class TrainBatchMaker:
             coef_off += RES * (4 + kx + ky)
             max_w, max_h = max(max_w, bw), max(max_h, bh)
         item_bytes = struct.calcsize(L.AUGMENT_ITEM_FORMAT)
-        table = torch.frombuffer(bytearray(b''.join(rows) + meta_mask.tobytes()), dtype=torch.uint8).to(dev)     # the one upload of the call
+        head = b''.join(rows) + meta_mask.tobytes()
+        if len(pastes):                                            # the int32 paste rows and row pointers ride behind the mask, 4-byte aligned
+            head += b'\0' * (-len(head) % 4)
+            pastes_off, ptr_off = len(head), len(head) + pastes.nbytes
+            head += pastes.tobytes() + paste_ptr.tobytes()
+        table = torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev)     # the one upload of the call
         new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
         rot_scratch = new(rot_off, dtype=torch.uint8) if rot_off else None
         mid_scratch, coef_scratch = new(mid_off, dtype=torch.uint8), new(coef_off, dtype=torch.int32)
         out = {'img': new(B, 3, RES, X_SLICE[1] - X_SLICE[0])}
         raw = new(B, RES, X_SLICE[1] - X_SLICE[0], 3, dtype=torch.uint8) if want_raw else None
-        L.augment_crop(table, B, max_w, max_h, rot_off > 0, rot_scratch, mid_scratch, coef_scratch, out['img'], raw, MEAN, STD)
+        if len(pastes):
+            L.augment_crop_occluded(table, B, max_w, max_h, rot_off > 0, rot_scratch, mid_scratch, coef_scratch, out['img'], raw, MEAN, STD,
+                                    self.bank.bank, self.bank.table, table.data_ptr() + pastes_off, table.data_ptr() + ptr_off, len(pastes))
+        else:
+            L.augment_crop(table, B, max_w, max_h, rot_off > 0, rot_scratch, mid_scratch, coef_scratch, out['img'], raw, MEAN, STD)
         if want_raw:
             out['img_u8'] = raw
         out.update(pose=new(B, 72), betas=new(B, 10), keypoints=new(B, 49, 3), keypoints_world=new(B, 49, 3), smpl_2dkps=new(B, 24, 3),
