@@ -795,6 +795,32 @@ int whmr_mesh_render_scene(const float* verts0, const float* verts1, int R, int 
                            long total_pixels, const void* grounds, const float* rot, float znear, float base_r, float base_g, float base_b,
                            float ambient, float k_d, float lx, float ly, float lz, float* scr, float* nrm, void* zbuf, int32_t* heights,
                            float* color_out, int32_t* face_out, float* depth_out, int32_t* ground_out, float* ground_y, void* stream);
+/* The marked form (same file, same device code): the scene plus keypoint skeletons and hidden-line wireframe, the --draw_keypoints and --wireframe of
+ * demo/whmr_demo.py:152,158 (cv2 and PARE's draw_skeleton are third-party: the drawing is defined in the kernel file's header and docs/kernels.md;
+ * pixel parity with cv2 is unpinned).  Two more DEVICE tables (asserted in csrc/mesh_render.hip as whmr_style_row / whmr_skeleton_row, restated
+ * by whmr_amd._lib.RENDER_STYLE_DTYPE / RENDER_SKELETON_DTYPE):
+ *   styles, D rows of 16 bytes (one per draw):  0 mode (int32, 0 solid, 1 wireframe)   4 half_width (float, pixels)   8 .. 15 reserved
+ *   skeletons, S rows of 32 bytes:  0 row (int32: row of joints / keypoints, cam_t and focal)   4 image (int32)   8 source (int32, 0: the 3-D joints
+ *     of the row are projected by the camera of the row, the image's centre, rot and the side rotation below; 1: the 2-D keypoints of the row)
+ *     12 layer (int32, 0 under the meshes, 1 over everything)   16 side_cos   20 side_sin (float)   24 half_width   28 radius (float, pixels)
+ * bones [NB, 2] int32 (joint indices; a bone with an index outside [0, J) is not drawn), bone_rgb [NB, 3], joint_rgb [J, 3] fp32 in 0..1 (device);
+ * joints [R, J, 3] fp32 in the mesh frame, keypoints [R, J, 3] fp32 = (x, y, confidence) in pixels of the target image (device; either may be null
+ * when no row uses it).  kp_out [max(S, 1), J, 3] fp32: (u, v, w) of every skeleton row, w > 0 = drawn (source 0: w = the depth Z if u, v, Z are
+ * finite and Z > znear; source 1: w = the confidence if x, y, confidence are finite; else 0) -- scratch that doubles as an output.  overlay_out
+ * [total_pixels, 3] fp32 or null: the blended colour of every pixel.  A mark covers the centre c of a pixel by a = clamp(half_width + 0.5 - d, 0, 1),
+ * d the distance from c to the bone's segment (radius and the distance to the joint for a joint dot), and blends C <- C + a (rgb - C), the skeletons
+ * of a layer in table order, bones before joints; a wireframe draw's face covers by its distance to the nearest of its three edges.  S = 0 with every
+ * style solid reproduces the bytes and planes of whmr_mesh_render_scene.  Joints are projected in launch 1, marks and wire alpha applied in launch 3:
+ * three launches, no allocation, no synchronisation, no float atomics; bit-reproducible.  WHMR_MESH_BIN_SKELETONS: the skeletons of one image that
+ * a workgroup of launch 3 bins into LDS; the ones beyond are tested pixel by pixel (same picture, slower). */
+#define WHMR_MESH_BIN_SKELETONS 16
+int whmr_mesh_render_marked(const float* verts0, const float* verts1, int R, int V, const int32_t* faces, int F, const int32_t* vf_ptr,
+                            const int32_t* vf_idx, const float* cam_t, const float* focal, const void* draws, int D, const void* images, int NI,
+                            long total_pixels, const void* grounds, const void* styles, const void* skeletons, int S, const int32_t* bones, int NB,
+                            const float* bone_rgb, const float* joint_rgb, int J, const float* joints, const float* keypoints, const float* rot,
+                            float znear, float base_r, float base_g, float base_b, float ambient, float k_d, float lx, float ly, float lz, float* scr,
+                            float* nrm, void* zbuf, int32_t* heights, float* kp_out, float* color_out, int32_t* face_out, float* depth_out,
+                            int32_t* ground_out, float* ground_y, float* overlay_out, void* stream);
 
 /* ---- training input side (csrc/augment.hip): the sample-making of BaseDataset.__getitem__ (datasets/base_dataset.py:249-384) for a whole batch --
  * rgb_processing (:183-207) over utils/imutils.py:crop (:54-88: integer box, skimage rotate, Pillow bicubic resize), Normalize and the

@@ -289,6 +289,8 @@ _SIGS = {
                                _P],
     'whmr_mesh_render_scene': [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P,
                                _P, _P, _P, _P, _P],
+    'whmr_mesh_render_marked': [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _F,
+                                _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     'whmr_iuv_losses': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     'whmr_iuv_losses_bwd': [_P, _I, _L, _P, _L, _L, _L, _L, _I, _I, _I, _F, _P, _P, _L, _P],
     'whmr_depth_loss': [_P, _I, _L, _I, _P, _L, _L, _L, _P, _I, _I, _I, _F, _P, _P, _P],
@@ -1073,6 +1075,91 @@ def mesh_render_scene(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, draws
                                         res['ground_y'].data_ptr(), _stream()), 'whmr_mesh_render_scene')
     if 'screen' in want:
         res['screen'] = scr[:D * V * 3].view(D, V, 3).clone()
+    return res
+
+
+# rows of the two further tables of whmr_mesh_render_marked (include/whmr_hip.h; asserted field by field in csrc/mesh_render.hip as whmr_style_row /
+# whmr_skeleton_row): one style per draw, one row per skeleton drawn
+RENDER_STYLE_DTYPE = np.dtype({'names': ['mode', 'half_width', 'reserved'], 'formats': ['<i4', '<f4', ('<i4', (2,))], 'offsets': [0, 4, 8], 'itemsize': 16})
+RENDER_SKELETON_DTYPE = np.dtype({'names': ['row', 'image', 'source', 'layer', 'side_cos', 'side_sin', 'half_width', 'radius'],
+                                  'formats': ['<i4', '<i4', '<i4', '<i4', '<f4', '<f4', '<f4', '<f4'], 'offsets': [0, 4, 8, 12, 16, 20, 24, 28],
+                                  'itemsize': 32})
+MESH_BIN_SKELETONS = 16                 # WHMR_MESH_BIN_SKELETONS: the skeletons of one image that a workgroup of the resolve launch bins; more are drawn all the same
+
+
+def _marked_keypoints(dev, n_floats):
+    """the (u, v, w) slots of whmr_mesh_render_marked, kept with the draw list's scratch per (device, stream) and grow-only in the same way"""
+    ws = _draw_ws.setdefault((dev, torch.cuda.current_stream(dev).cuda_stream), {'scr': None, 'nrm': None, 'zbuf': None, 'retired': []})
+    k = ws.get('kp')
+    if k is None or k.numel() < n_floats:
+        if k is not None:
+            ws['retired'].append(k)
+        k = ws['kp'] = torch.empty(max(n_floats, 2 * k.numel() if k is not None else 1), dtype=torch.float32, device=dev)
+    return k
+
+
+def mesh_render_marked(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, draws, n_draws, images, n_images, total_pixels, grounds, styles, skeletons,
+                       n_skeletons, bones, bone_rgb, joint_rgb, joints, keypoints, color, rot=None, znear=0.05, ambient=0.3,
+                       k_d=4 * (1 - 0.2) * (1 - 0.04) / math.pi, light=(0.0, 0.0, 1.0), want=()):
+    """``mesh_render_scene`` with keypoint skeletons and hidden-line wireframe (include/whmr_hip.h: whmr_mesh_render_marked; the drawing is defined in
+    csrc/mesh_render.hip and docs/kernels.md).  styles: uint8 DEVICE tensor of ``n_draws`` RENDER_STYLE_DTYPE rows; skeletons: of ``n_skeletons``
+    RENDER_SKELETON_DTYPE rows (MeshRenderer.plan_styles / plan_skeletons pack them); bones [NB, 2] int32, bone_rgb [NB, 3], joint_rgb [J, 3] fp32;
+    joints / keypoints [R, J, 3] fp32 or None (a source no row uses).  Returns the dict of ``mesh_render_scene`` with, if asked for in ``want``,
+    'overlay' [total_pixels, 3] fp32 (the blended colour of every pixel) and 'keypoints' [n_skeletons, J, 3] fp32 = (u, v, w) of every skeleton row,
+    w > 0 where the joint is drawn.  The same three launches; the scratch is kept per (device, stream) and only grows; nothing is read back."""
+    _dev(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, draws, images, grounds, styles, skeletons, bones, bone_rgb, joint_rgb, joints, keypoints)
+    R, V = verts0.shape[0], verts0.shape[1]
+    F = faces.shape[0]
+    D, NI, total, S = int(n_draws), int(n_images), int(total_pixels), int(n_skeletons)
+    NB, J = bones.shape[0], joint_rgb.shape[0]
+    for v in (verts0, verts1):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == (R, V, 3))
+    assert cam_t.dtype == torch.float32 and cam_t.is_contiguous() and tuple(cam_t.shape) == (R, 3)
+    assert focal.dtype == torch.float32 and focal.is_contiguous() and tuple(focal.shape) == (R, 2)
+    assert faces.dtype == torch.int32 and faces.is_contiguous() and faces.dim() == 2 and faces.shape[1] == 3
+    assert vf_ptr.dtype == torch.int32 and vf_ptr.is_contiguous() and vf_ptr.numel() == V + 1
+    assert vf_idx.dtype == torch.int32 and vf_idx.is_contiguous() and vf_idx.numel() == 3 * F
+    assert draws.dtype == torch.uint8 and draws.is_contiguous() and draws.numel() == D * RENDER_DRAW_DTYPE.itemsize
+    assert images.dtype == torch.uint8 and images.is_contiguous() and images.numel() == NI * RENDER_IMAGE_DTYPE.itemsize
+    assert grounds.dtype == torch.uint8 and grounds.is_contiguous() and grounds.numel() == NI * RENDER_GROUND_DTYPE.itemsize
+    assert styles.dtype == torch.uint8 and styles.is_contiguous() and styles.numel() == D * RENDER_STYLE_DTYPE.itemsize
+    assert skeletons.dtype == torch.uint8 and skeletons.is_contiguous() and skeletons.numel() == S * RENDER_SKELETON_DTYPE.itemsize
+    assert bones.dtype == torch.int32 and bones.is_contiguous() and tuple(bones.shape) == (NB, 2)
+    assert bone_rgb.dtype == torch.float32 and bone_rgb.is_contiguous() and tuple(bone_rgb.shape) == (NB, 3)
+    assert joint_rgb.dtype == torch.float32 and joint_rgb.is_contiguous() and tuple(joint_rgb.shape) == (J, 3) and J >= 1
+    for v in (joints, keypoints):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == (R, J, 3))
+    assert S == 0 or joints is not None or keypoints is not None
+    assert R >= 1 and D >= 0 and S >= 0 and 1 <= NI <= 65535 and total >= 1 and D * F < 2 ** 31 and S * J < 2 ** 31
+    unknown = set(want) - {'color', 'face', 'depth', 'screen', 'ground', 'overlay', 'keypoints'}
+    assert not unknown, 'unknown outputs %s' % sorted(unknown)
+    dev = verts0.device
+    scr, nrm, zbuf = _draw_workspace(dev, max(D, 1) * V * 3, total)
+    heights = _scene_heights(dev, max(D, 1))
+    kp = _marked_keypoints(dev, max(S, 1) * J * 3)
+    res = {'ground_y': torch.empty(NI, dtype=torch.float32, device=dev)}
+    for k, shape, dtype in (('color', (total, 3), torch.float32), ('face', (total,), torch.int32), ('depth', (total,), torch.float32),
+                            ('ground', (total,), torch.int32), ('overlay', (total, 3), torch.float32)):
+        if k in want:
+            res[k] = torch.empty(shape, dtype=dtype, device=dev)
+    rot_c = None
+    if rot is not None:
+        r = [float(v) for row in rot for v in row]
+        assert len(r) == 9
+        rot_c = (C.c_float * 9)(*r)
+    lx, ly, lz = (float(v) for v in light)
+    _check(lib().whmr_mesh_render_marked(verts0.data_ptr(), _ptr(verts1), R, V, faces.data_ptr(), F, vf_ptr.data_ptr(), vf_idx.data_ptr(), cam_t.data_ptr(),
+                                         focal.data_ptr(), draws.data_ptr(), D, images.data_ptr(), NI, total, grounds.data_ptr(), styles.data_ptr(),
+                                         skeletons.data_ptr(), S, bones.data_ptr(), NB, bone_rgb.data_ptr(), joint_rgb.data_ptr(), J, _ptr(joints),
+                                         _ptr(keypoints), C.cast(rot_c, C.c_void_p) if rot_c is not None else None, float(znear), float(color[0]),
+                                         float(color[1]), float(color[2]), float(ambient), float(k_d), lx, ly, lz, scr.data_ptr(), nrm.data_ptr(),
+                                         zbuf.data_ptr(), heights.data_ptr(), kp.data_ptr(), _ptr(res.get('color')), _ptr(res.get('face')),
+                                         _ptr(res.get('depth')), _ptr(res.get('ground')), res['ground_y'].data_ptr(), _ptr(res.get('overlay')), _stream()),
+           'whmr_mesh_render_marked')
+    if 'screen' in want:
+        res['screen'] = scr[:D * V * 3].view(D, V, 3).clone()
+    if 'keypoints' in want:
+        res['keypoints'] = kp[:S * J * 3].view(S, J, 3).clone()
     return res
 
 

@@ -27,3 +27,17 @@ J24_FLIP_PERM = [5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13, 14, 15, 16, 17, 1
 OPENPOSE25_FLIP_PERM = [0, 1, 5, 6, 7, 2, 3, 4, 8, 12, 13, 14, 9, 10, 11, 16, 15, 18, 17, 22, 23, 24, 19, 20, 21]
 J49_FLIP_PERM = OPENPOSE25_FLIP_PERM + [25 + j for j in J24_FLIP_PERM]
 SMPL_J49_FLIP_PERM = OPENPOSE25_FLIP_PERM + [25 + j for j in SMPL_JOINTS_FLIP_PERM]
+
+# The 25 bones of the keypoint skeleton the demo draws (--draw_keypoints): the joint pairs of get_spin_skeleton() (datasets/data_utils/kp_utils.py:286
+# in the reference) over the 49 joints above -- the OpenPose body, face and feet, and nose -> head top.  tests/golden/skeleton.npz holds the table.
+SPIN_SKELETON = [(0, 1), (1, 2), (2, 3), (3, 4), (1, 5), (5, 6), (6, 7), (1, 8), (8, 9), (9, 10), (10, 11), (8, 12), (12, 13), (13, 14), (0, 15), (0, 16),
+                 (15, 17), (16, 18), (21, 19), (19, 20), (14, 21), (11, 24), (24, 22), (22, 23), (0, 38)]
+# The side of every bone, from the names of get_spin_joint_names() (:212): 'l' / 'r' if one of its two joints is a left / right one ('OP LKnee',
+# 'OP RHeel', ...; no bone joins a left joint to a right one), 'c' for the trunk, the neck and the head top.
+SPIN_BONE_SIDE = 'crrrlllcrrrlllrlrllllrrrc'
+# How the skeleton is drawn is this package's choice (the reference draws it with PARE's draw_skeleton on cv2, neither of them in its tree): the
+# person's left warm, the right cold, the centre line yellow, joints white; widths in pixels.
+SKELETON_SIDE_RGB = {'l': (1.0, 0.45, 0.2), 'r': (0.2, 0.7, 1.0), 'c': (0.95, 0.9, 0.3)}
+SKELETON_JOINT_RGB = (1.0, 1.0, 1.0)
+SKELETON_BONE_WIDTH, SKELETON_JOINT_RADIUS = 3.0, 3.0
+WIREFRAME_LINE_WIDTH = 1.0

@@ -43,13 +43,12 @@
 
 struct mesh_cam { float cx, cy, sc, ss; int has_rot; float r[9]; };
 
-// The vertex transform of launch 1, one code path for both entry points: vertex v of the mesh at vp (mesh frame) under camera c with translation t and
-// focal lengths fo -> its screen position (u, v, depth) and its world-frame smooth normal.
-__device__ __forceinline__ void mesh_vertex(const float* __restrict__ vp, int v, const int32_t* __restrict__ faces, const int32_t* __restrict__ vf_ptr,
-                                            const int32_t* __restrict__ vf_idx, const float* __restrict__ t, const float* __restrict__ fo, const mesh_cam& c,
-                                            float* __restrict__ scr, float* __restrict__ nrm) {
+// The camera of launch 1, one code path for vertices and skeleton joints: the point p (mesh frame) under camera c with translation t and focal
+// lengths fo -> its screen position (u, v, depth).
+__device__ __forceinline__ void mesh_camera(const float* __restrict__ p, const float* __restrict__ t, const float* __restrict__ fo, const mesh_cam& c,
+                                            float* __restrict__ scr) {
     // world: q = S D p,  S = [[c, 0, s], [0, 1, 0], [-s, 0, c]]
-    const float x = vp[v * 3], y = -vp[v * 3 + 1], z = -vp[v * 3 + 2];
+    const float x = p[0], y = -p[1], z = -p[2];
     const float qx = c.sc * x + c.ss * z, qy = y, qz = c.sc * z - c.ss * x;
     float px = qx, py = qy, pz = qz;
     if (c.has_rot) {                                                              // p_c = R^T q
@@ -61,6 +60,14 @@ __device__ __forceinline__ void mesh_vertex(const float* __restrict__ vp, int v,
     scr[0] = c.cx + fo[0] * X / Z;
     scr[1] = c.cy + fo[1] * Y / Z;
     scr[2] = Z;
+}
+
+// The vertex transform of launch 1, one code path for both entry points: vertex v of the mesh at vp (mesh frame) under camera c with translation t and
+// focal lengths fo -> its screen position (u, v, depth) and its world-frame smooth normal.
+__device__ __forceinline__ void mesh_vertex(const float* __restrict__ vp, int v, const int32_t* __restrict__ faces, const int32_t* __restrict__ vf_ptr,
+                                            const int32_t* __restrict__ vf_idx, const float* __restrict__ t, const float* __restrict__ fo, const mesh_cam& c,
+                                            float* __restrict__ scr, float* __restrict__ nrm) {
+    mesh_camera(vp + v * 3, t, fo, c, scr);
     float nx = 0.f, ny = 0.f, nz = 0.f;
     for (int k = vf_ptr[v]; k < vf_ptr[v + 1]; ++k) {
         const int32_t* f = faces + (size_t)vf_idx[k] * 3;
@@ -648,6 +655,357 @@ extern "C" int whmr_mesh_render_scene(const float* verts0, const float* verts1, 
     const long mean_plane = (total_pixels + NI - 1) / NI;
     hipLaunchKernelGGL(mesh_scene_resolve_kernel, dim3((unsigned)((mean_plane + 255) / 256), (unsigned)NI), dim3(256), 0, st, scr, nrm, faces,
                        (const unsigned long long*)zbuf, color_out, face_out, depth_out, cam_t, focal, V, F, znear, tg, m, c, sc);
+    WHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// Marked form: the scene plus keypoint skeletons (--draw_keypoints, demo/whmr_demo.py:158; the keypoints_2d of render_image_group,
+// utils/renderer_cam.py:157,165-166) and hidden-line wireframe (--wireframe, :152).  The reference draws the skeleton with PARE's draw_skeleton on cv2
+// lines and circles; neither is in the reference tree, so the drawing is DEFINED here and pixel parity with cv2 is unpinned.  Pixel (j, i) has the
+// centre c = (i + 0.5, j + 0.5).
+//   Keypoints of a skeleton row: source 0 sends the row's 3-D joints (mesh frame) through mesh_camera with the row's cam_t / focal, the target image's
+//   centre, the call's rot and the row's side rotation: (u, v, Z), valid with w = Z if u, v, Z are finite and Z > znear, else w = 0.  Source 1 takes the
+//   row's 2-D keypoints (x, y, conf): w = conf, or 0 if one of the three is not finite.  (u, v, w) of every row goes to kp [S, J, 3].
+//   Coverage: a bone (n0, n1) is drawn iff both w > 0 and covers c by a = clamp(half_width + 0.5 - d, 0, 1), d the distance from c to the segment (the
+//   foot parameter clamped to [0, 1]; a bone of no length is a point).  A joint with w > 0 covers by a = clamp(radius + 0.5 - |c - k|, 0, 1).  A bone
+//   naming a joint outside [0, J) is not drawn.
+//   A layer at a pixel: from a colour C, the skeletons of this image and this layer in table order, in each the bones in table order and then the
+//   joints in index order; each with a > 0 blends C <- C + a (rgb - C).
+//   The pixel: C0 = frame / 255 (0 without a frame); C1 = the under layer over C0; the scene's sample (z-buffer winner or plane) as today, with alpha 1
+//   for a solid draw and the plane and, for a wireframe draw, alpha = clamp(half_width + 0.5 - d_e, 0, 1), d_e = the smallest of |edge function at c| /
+//   the edge's screen length over the winner's three edges -- the winner is still the nearest face, so hidden lines stay hidden; an inner edge is
+//   drawn by both its faces (2 half_width wide), a silhouette edge by one.  C2 = the shaded colour exactly where alpha = 1, C1 where alpha = 0 or
+//   nothing won, else C1 + alpha (shade - C1); C3 = the over layer over C2.  Bytes: the frame's where nothing touched the pixel, today's where alpha = 1
+//   and no over mark touched it, rint(255 C3) elsewhere.  color / face / depth / ground keep the winner's sample whatever its alpha.
+// The resolve does not test every pixel against every bone: a workgroup lists the skeletons of its own image once (wave 0, ballots, table order),
+// and for each span of 256 pixels marks in LDS bit masks -- one bit per (listed skeleton, bone or joint), one mask per layer -- the ones whose box,
+// padded by half-width or radius + 0.5, meets the span's box.  A pixel walks the set bits in order.  The list holds MESH_BIN_SKELETONS skeletons (and
+// no more than fit MESH_BIN_WORDS mask words); the skeletons of the image beyond it come later in table order and are tested pixel by pixel after it.
+struct whmr_style_row {
+    int32_t mode;                               // 0 solid, 1 wireframe
+    float half_width;                           // of a wireframe line, pixels
+    int32_t reserved[2];
+};
+struct whmr_skeleton_row {
+    int32_t row;                                // row of joints / keypoints, cam_t and focal
+    int32_t image;                              // target image
+    int32_t source;                             // 0: project the 3-D joints of the row, 1: the 2-D keypoints of the row
+    int32_t layer;                              // 0 under the meshes, 1 over everything
+    float side_cos, side_sin;                   // of the side rotation (source 0)
+    float half_width, radius;                   // of a bone / a joint dot, pixels
+};
+static_assert(sizeof(whmr_style_row) == 16, "table layout");
+static_assert(offsetof(whmr_style_row, mode) == 0, "table layout");
+static_assert(offsetof(whmr_style_row, half_width) == 4, "table layout");
+static_assert(offsetof(whmr_style_row, reserved) == 8, "table layout");
+static_assert(sizeof(whmr_skeleton_row) == 32, "table layout");
+static_assert(offsetof(whmr_skeleton_row, row) == 0, "table layout");
+static_assert(offsetof(whmr_skeleton_row, image) == 4, "table layout");
+static_assert(offsetof(whmr_skeleton_row, source) == 8, "table layout");
+static_assert(offsetof(whmr_skeleton_row, layer) == 12, "table layout");
+static_assert(offsetof(whmr_skeleton_row, side_cos) == 16, "table layout");
+static_assert(offsetof(whmr_skeleton_row, side_sin) == 20, "table layout");
+static_assert(offsetof(whmr_skeleton_row, half_width) == 24, "table layout");
+static_assert(offsetof(whmr_skeleton_row, radius) == 28, "table layout");
+
+#define MESH_BIN_SKELETONS 16                   // include/whmr_hip.h: WHMR_MESH_BIN_SKELETONS, whmr_amd._lib.MESH_BIN_SKELETONS
+#define MESH_BIN_WORDS 32                       // 2048 (skeleton, bone or joint) bits per layer
+
+struct mesh_marks {
+    const whmr_style_row* styles;            // [D]
+    const whmr_skeleton_row* skels;          // [S]
+    const int32_t* bones;                       // [NB, 2]
+    const float *bone_rgb, *joint_rgb;          // [NB, 3], [J, 3]
+    const float *joints, *keypoints;            // [R, J, 3] each, or null
+    float* kp;                                  // [S, J, 3]: (u, v, w)
+    float* overlay;                             // [total_pixels, 3] or null
+    int S, NB, J, R;
+    // the image of skeleton s, or -1 (a row the host would have refused: nothing is read through it, nothing of it is drawn)
+    __device__ __forceinline__ int image(int s, const mesh_draw_targets& tg) const {
+        const whmr_skeleton_row& k = skels[s];
+        const bool ok = (unsigned)k.row < (unsigned)R && (unsigned)k.layer < 2u && ((k.source == 0 && joints) || (k.source == 1 && keypoints)) &&
+                        tg.image_ok(k.image);
+        return ok ? k.image : -1;
+    }
+};
+
+// The scene's sample of one pixel as mesh_scene_resolve_kernel takes it (that kernel keeps its own text, and with it its code object, as it was): the
+// z-buffer's winner, or the plane where it is nearer (tile >= 0).
+__device__ __forceinline__ mesh_sample mesh_scene_sample(unsigned long long key, int x, int y, const float* __restrict__ scr, const float* __restrict__ nrm,
+                                                         const int32_t* __restrict__ faces, int V, int F, const mesh_shade& m, const mesh_plane& pl,
+                                                         const mesh_cam& c, float cx, float cy, float znear, int& tile) {
+    mesh_sample s = mesh_resolve(key, x, y, scr, nrm, faces, V, F, m);
+    tile = -1;
+    if (pl.on) {
+        float Z;
+        int ix, iz;
+        if (mesh_plane_hit(pl, c, cx, cy, x, y, znear, Z, ix, iz) && (!s.hit || Z < s.depth)) {
+            const float grey = ((ix + iz) & 1) ? pl.light : pl.dark;
+            s = mesh_sample{-1, grey, grey, grey, Z, true};
+            tile = ix * (int)pl.n + iz;
+        }
+    }
+    return s;
+}
+
+__device__ __forceinline__ bool mesh_finite(float f) { return fabsf(f) < __builtin_inff(); }                      // false for a NaN
+
+// Launch 1 of the marked form: as the scene's, and thread idx < S * J writes (u, v, w) of joint idx % J of skeleton row idx / J.
+__global__ __launch_bounds__(256) void mesh_marked_vertex_kernel(const float* __restrict__ verts0, const float* __restrict__ verts1, const int32_t* __restrict__ faces,
+                                                                 const int32_t* __restrict__ vf_ptr, const int32_t* __restrict__ vf_idx,
+                                                                 const float* __restrict__ cam_t, const float* __restrict__ focal, float* __restrict__ scr,
+                                                                 float* __restrict__ nrm, unsigned long long* __restrict__ zbuf, int D, int V, mesh_draw_targets tg,
+                                                                 mesh_cam c, int32_t* __restrict__ heights, mesh_marks mk, float znear) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < tg.total) zbuf[idx] = ~0ull;
+    if (idx < D) heights[idx] = MESH_NO_HEIGHT;
+    if (idx < (long)mk.S * mk.J) {
+        const int s = (int)(idx / mk.J), j = (int)(idx - (long)s * mk.J);
+        float u = 0.f, v = 0.f, w = 0.f;
+        const int img = mk.image(s, tg);
+        if (img >= 0) {
+            const whmr_skeleton_row k = mk.skels[s];
+            if (k.source == 0) {
+                mesh_cam cj = c;
+                cj.cx = tg.images[img].cx; cj.cy = tg.images[img].cy; cj.sc = k.side_cos; cj.ss = k.side_sin;
+                float o[3];
+                mesh_camera(mk.joints + ((size_t)k.row * mk.J + j) * 3, cam_t + (size_t)k.row * 3, focal + (size_t)k.row * 2, cj, o);
+                u = o[0]; v = o[1];
+                w = (mesh_finite(u) && mesh_finite(v) && mesh_finite(o[2]) && o[2] > znear) ? o[2] : 0.f;
+            } else {
+                const float* q = mk.keypoints + ((size_t)k.row * mk.J + j) * 3;
+                u = q[0]; v = q[1];
+                w = (mesh_finite(u) && mesh_finite(v) && mesh_finite(q[2])) ? q[2] : 0.f;
+            }
+        }
+        mk.kp[idx * 3] = u; mk.kp[idx * 3 + 1] = v; mk.kp[idx * 3 + 2] = w;
+    }
+    mesh_draw_vertex(verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, scr, nrm, idx, D, V, tg, c);
+}
+
+// coverage of the centre (px, py) by the segment a -> b of reach = half-width + 0.5 (a == b: a dot)
+__device__ __forceinline__ float mesh_cover(float px, float py, float ax, float ay, float bx, float by, float reach) {
+    const float dx = bx - ax, dy = by - ay, len2 = dx * dx + dy * dy;
+    float t = 0.f;
+    if (len2 > 0.f) t = fminf(fmaxf(((px - ax) * dx + (py - ay) * dy) / len2, 0.f), 1.f);
+    const float ex = px - (ax + t * dx), ey = py - (ay + t * dy);
+    return fminf(fmaxf(reach - sqrtf(ex * ex + ey * ey), 0.f), 1.f);              // fmaxf drops a NaN: not covered
+}
+
+// Element e of skeleton row s (e < NB: bone e, else joint e - NB): false = not drawn; else its end points, reach and colour.
+struct mesh_mark_geom { float ax, ay, bx, by, reach; const float* rgb; };
+__device__ __forceinline__ bool mesh_mark_of(const mesh_marks& mk, int s, int e, mesh_mark_geom& g) {
+    const whmr_skeleton_row& sk = mk.skels[s];
+    const float* k = mk.kp + (size_t)s * mk.J * 3;
+    if (e < mk.NB) {
+        const int n0 = mk.bones[2 * e], n1 = mk.bones[2 * e + 1];
+        if ((unsigned)n0 >= (unsigned)mk.J || (unsigned)n1 >= (unsigned)mk.J) return false;
+        const float *k0 = k + n0 * 3, *k1 = k + n1 * 3;
+        if (!(k0[2] > 0.f && k1[2] > 0.f)) return false;
+        g = mesh_mark_geom{k0[0], k0[1], k1[0], k1[1], sk.half_width + 0.5f, mk.bone_rgb + 3 * e};
+        return true;
+    }
+    const int j = e - mk.NB;
+    const float* k0 = k + j * 3;
+    if (!(k0[2] > 0.f)) return false;
+    g = mesh_mark_geom{k0[0], k0[1], k0[0], k0[1], sk.radius + 0.5f, mk.joint_rgb + 3 * j};
+    return true;
+}
+// one mark over the colour (c0, c1, c2) at the centre (px, py)
+__device__ __forceinline__ void mesh_mark(const mesh_marks& mk, int s, int e, float px, float py, float& c0, float& c1, float& c2, bool& touched) {
+    mesh_mark_geom g;
+    if (!mesh_mark_of(mk, s, e, g)) return;
+    const float a = mesh_cover(px, py, g.ax, g.ay, g.bx, g.by, g.reach);
+    if (a > 0.f) {
+        c0 = __fmaf_rn(a, g.rgb[0] - c0, c0); c1 = __fmaf_rn(a, g.rgb[1] - c1, c1); c2 = __fmaf_rn(a, g.rgb[2] - c2, c2);
+        touched = true;
+    }
+}
+// can the mark reach a centre inside the box [x0, x1] x [y0, y1]?  Its own box, padded by the reach and a little more than rounding can lose:
+// a superset of the covered centres is all the binning needs, the pixel decides.
+__device__ __forceinline__ bool mesh_mark_meets(const mesh_marks& mk, int s, int e, float x0, float y0, float x1, float y1) {
+    mesh_mark_geom g;
+    if (!mesh_mark_of(mk, s, e, g)) return false;
+    const float pad = g.reach + 0.0625f;
+    return fminf(g.ax, g.bx) - pad <= x1 && fmaxf(g.ax, g.bx) + pad >= x0 && fminf(g.ay, g.by) - pad <= y1 && fmaxf(g.ay, g.by) + pad >= y0;
+}
+
+// one layer at one pixel: the binned marks in bit order (= table order), then the skeletons that did not fit the list, element by element
+__device__ __forceinline__ void mesh_layer(const mesh_marks& mk, const mesh_draw_targets& tg, int img, int layer, const unsigned long long* words, int nwords,
+                                           const int* list, int E, int s_over, float px, float py, float& c0, float& c1, float& c2, bool& touched) {
+    for (int w = 0; w < nwords; ++w) {
+        const unsigned long long word = words[w];
+        // the same word in every lane: the walk is wave-uniform
+        unsigned long long m = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(word >> 32)) << 32) |
+                               (unsigned)__builtin_amdgcn_readfirstlane((int)(word & 0xffffffffu));
+        while (m) {
+            const int i = w * 64 + __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const int k = i / E;
+            mesh_mark(mk, __builtin_amdgcn_readfirstlane(list[k]), i - k * E, px, py, c0, c1, c2, touched);
+        }
+    }
+    for (int s = s_over; s < mk.S; ++s) {
+        if (mk.image(s, tg) != img || mk.skels[s].layer != layer) continue;
+        for (int e = 0; e < E; ++e) mesh_mark(mk, s, e, px, py, c0, c1, c2, touched);
+    }
+}
+
+// alpha of a wireframe draw's winning face gid at pixel (x, y)
+__device__ __forceinline__ float mesh_wire_alpha(int gid, int x, int y, const float* __restrict__ scr, const int32_t* __restrict__ faces, int V, int F,
+                                                 float half_width) {
+    const int p = gid / F, f = gid - p * F;
+    const float* s = scr + (size_t)p * V * 3;
+    const float *a = s + (size_t)faces[f * 3] * 3, *b = s + (size_t)faces[f * 3 + 1] * 3, *d = s + (size_t)faces[f * 3 + 2] * 3;
+    const float px = x + 0.5f, py = y + 0.5f;
+    const float d0 = fabsf(mesh_edge(b[0], b[1], d[0], d[1], px, py)) / sqrtf((d[0] - b[0]) * (d[0] - b[0]) + (d[1] - b[1]) * (d[1] - b[1]));
+    const float d1 = fabsf(mesh_edge(d[0], d[1], a[0], a[1], px, py)) / sqrtf((a[0] - d[0]) * (a[0] - d[0]) + (a[1] - d[1]) * (a[1] - d[1]));
+    const float d2 = fabsf(mesh_edge(a[0], a[1], b[0], b[1], px, py)) / sqrtf((b[0] - a[0]) * (b[0] - a[0]) + (b[1] - a[1]) * (b[1] - a[1]));
+    return fminf(fmaxf(half_width + 0.5f - fminf(d0, fminf(d1, d2)), 0.f), 1.f);                // fminf skips the 0 / 0 of an edge without length
+}
+
+__device__ __forceinline__ uint8_t mesh_byte(float c) { return (uint8_t)rintf(255.f * __builtin_amdgcn_fmed3f(c, 0.f, 1.f)); }
+
+// Launch 3 of the marked form: the scene's resolve with the two mark layers and the wire alpha (see the header of this section).
+__global__ __launch_bounds__(256) void mesh_marked_resolve_kernel(const float* __restrict__ scr, const float* __restrict__ nrm, const int32_t* __restrict__ faces,
+                                                                  const unsigned long long* __restrict__ zbuf, float* __restrict__ color_out,
+                                                                  int32_t* __restrict__ face_out, float* __restrict__ depth_out, const float* __restrict__ cam_t,
+                                                                  const float* __restrict__ focal, int V, int F, float znear, mesh_draw_targets tg, mesh_shade m,
+                                                                  mesh_cam c, mesh_scene sc, mesh_marks mk) {
+    __shared__ unsigned long long s_words[2][MESH_BIN_WORDS];
+    __shared__ int s_list[MESH_BIN_SKELETONS];
+    __shared__ int s_n, s_over;
+    const int img = (int)blockIdx.y, tid = (int)threadIdx.x, lane = tid & 63;
+    const bool first = blockIdx.x == 0 && tid == 0;
+    if (!tg.image_ok(img)) {                                                      // block-uniform
+        if (first) sc.ground_y[img] = __builtin_nanf("");
+        return;
+    }
+    const whmr_render_image im = tg.images[img];
+    const mesh_plane pl = mesh_plane_setup(img, tg, sc, cam_t, focal, c);
+    if (first) sc.ground_y[img] = pl.on ? pl.h : __builtin_nanf("");
+    const long plane = (long)im.H * im.W;
+    // the skeletons of this image, in table order: the first `fit` into the list, the first one beyond it into s_over
+    const int E = mk.NB + mk.J;
+    int n_bin = 0, over = mk.S;
+    if (mk.S > 0) {                                                               // kernel-uniform
+        const int room = MESH_BIN_WORDS * 64 / E, fit = room < MESH_BIN_SKELETONS ? room : MESH_BIN_SKELETONS;
+        if (tid < 64) {
+            int count = 0;
+            if (lane == 0) s_over = mk.S;
+            for (int s0 = 0; s0 < mk.S; s0 += 64) {
+                const int s = s0 + lane;
+                const bool mine = s < mk.S && mk.image(s, tg) == img;
+                const unsigned long long b = __ballot(mine);
+                const int pos = count + __popcll(b & ((1ull << lane) - 1ull));
+                if (mine && pos < fit) s_list[pos] = s;
+                if (mine && pos == fit) s_over = s;
+                count += __popcll(b);
+            }
+            if (lane == 0) s_n = count < fit ? count : fit;
+        }
+        __syncthreads();
+        n_bin = s_n; over = s_over;
+    }
+    const bool marks = n_bin > 0 || over < mk.S;                                   // block-uniform
+    const int n_items = n_bin * E, nwords = (n_items + 63) >> 6;                  // <= MESH_BIN_WORDS
+    for (long r0 = (long)blockIdx.x * 256; r0 < plane; r0 += (long)gridDim.x * 256) {          // block-uniform bounds: every thread meets the barriers
+        if (nwords > 0) {
+            __syncthreads();                                                      // the previous span has been read
+            const long r1 = r0 + 255 < plane ? r0 + 255 : plane - 1;
+            const int ya = (int)(r0 / im.W), yb = (int)(r1 / im.W);
+            const float x0 = ya == yb ? (float)(r0 - (long)ya * im.W) + 0.5f : 0.5f, x1 = ya == yb ? (float)(r1 - (long)yb * im.W) + 0.5f : (float)im.W - 0.5f;
+            const float y0 = (float)ya + 0.5f, y1 = (float)yb + 0.5f;
+            for (int i0 = 0; i0 < nwords * 64; i0 += 256) {
+                const int i = i0 + tid;
+                int layer = -1;
+                if (i < n_items) {
+                    const int k = i / E, s = s_list[k];
+                    if (mesh_mark_meets(mk, s, i - k * E, x0, y0, x1, y1)) layer = mk.skels[s].layer;
+                }
+                const unsigned long long under = __ballot(layer == 0), above = __ballot(layer == 1);
+                if (lane == 0 && (i >> 6) < nwords) { s_words[0][i >> 6] = under; s_words[1][i >> 6] = above; }
+            }
+            __syncthreads();
+        }
+        const long r = r0 + tid;
+        if (r < plane) {
+            const int y = (int)(r / im.W), x = (int)(r - (long)y * im.W);
+            const long at = im.pix_off + r;
+            const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+            const uint8_t* fr = im.frame ? im.frame + y * im.frame_row_stride + (long)x * 3 : nullptr;
+            uint8_t* o = im.out + y * im.out_row_stride + (long)x * 3;
+            float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+            if (fr) { c0 = (float)fr[0] / 255.f; c1 = (float)fr[1] / 255.f; c2 = (float)fr[2] / 255.f; }
+            bool under = false, above = false;
+            if (marks) mesh_layer(mk, tg, img, 0, s_words[0], nwords, s_list, E, over, px, py, c0, c1, c2, under);
+            int tile;
+            const mesh_sample s = mesh_scene_sample(zbuf[at], x, y, scr, nrm, faces, V, F, m, pl, c, im.cx, im.cy, znear, tile);
+            float alpha = s.hit ? 1.f : 0.f;
+            if (s.hit && s.gid >= 0) {
+                const whmr_style_row st = mk.styles[s.gid / F];
+                if (st.mode == 1) alpha = mesh_wire_alpha(s.gid, x, y, scr, faces, V, F, st.half_width);
+            }
+            if (alpha == 1.f) {
+                c0 = s.c0; c1 = s.c1; c2 = s.c2;
+            } else if (alpha > 0.f) {
+                c0 = __fmaf_rn(alpha, s.c0 - c0, c0); c1 = __fmaf_rn(alpha, s.c1 - c1, c1); c2 = __fmaf_rn(alpha, s.c2 - c2, c2);
+            }
+            if (marks) mesh_layer(mk, tg, img, 1, s_words[1], nwords, s_list, E, over, px, py, c0, c1, c2, above);
+            mesh_store(s, o, fr, at, color_out, face_out, depth_out);            // today's bytes and planes
+            const bool today = !above && (s.hit ? alpha == 1.f : !under);
+            if (!today) {
+                if (!under && !above && alpha == 0.f) {                           // a wireframe face away from its edges: nothing touched the pixel
+                    o[0] = fr ? fr[0] : 0; o[1] = fr ? fr[1] : 0; o[2] = fr ? fr[2] : 0;
+                } else {
+                    o[0] = mesh_byte(c0); o[1] = mesh_byte(c1); o[2] = mesh_byte(c2);
+                }
+            }
+            if (sc.ground_out) sc.ground_out[at] = tile;
+            if (mk.overlay) { mk.overlay[at * 3] = c0; mk.overlay[at * 3 + 1] = c1; mk.overlay[at * 3 + 2] = c2; }
+        }
+    }
+}
+
+// The arguments of whmr_mesh_render_scene, and: styles: DEVICE table of D whmr_style_row; skeletons: DEVICE table of S whmr_skeleton_row (S may
+// be 0); bones [NB, 2] int32, bone_rgb [NB, 3], joint_rgb [J, 3], joints / keypoints [R, J, 3] (either may be null when no row uses it): device;
+// kp_out [max(S, 1), J, 3] fp32: (u, v, w) of every skeleton row; overlay_out [total_pixels, 3] fp32 or null: the blended colour C3 of every pixel.
+// Launch 2 is the scene's own kernel.  Three launches, no allocation, no synchronisation, no float atomics; bit-reproducible.
+extern "C" int whmr_mesh_render_marked(const float* verts0, const float* verts1, int R, int V, const int32_t* faces, int F, const int32_t* vf_ptr,
+                                       const int32_t* vf_idx, const float* cam_t, const float* focal, const void* draws, int D, const void* images, int NI,
+                                       long total_pixels, const void* grounds, const void* styles, const void* skeletons, int S, const int32_t* bones, int NB,
+                                       const float* bone_rgb, const float* joint_rgb, int J, const float* joints, const float* keypoints, const float* rot,
+                                       float znear, float base_r, float base_g, float base_b, float ambient, float k_d, float lx, float ly, float lz,
+                                       float* scr, float* nrm, void* zbuf, int32_t* heights, float* kp_out, float* color_out, int32_t* face_out,
+                                       float* depth_out, int32_t* ground_out, float* ground_y, float* overlay_out, void* stream) {
+    if (R <= 0 || V <= 0 || F <= 0 || D < 0 || NI <= 0 || NI > 65535 || total_pixels <= 0 || (long)D * F > 0x7fffffffL || !grounds || !heights || !ground_y)
+        return (int)hipErrorInvalidValue;
+    if (S < 0 || NB < 0 || J < 0 || (D > 0 && !styles) || (NB > 0 && (!bones || !bone_rgb)) || (long)S * J > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    if (S > 0 && (!skeletons || J < 1 || !joint_rgb || !kp_out || (!joints && !keypoints))) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    mesh_cam c{0.f, 0.f, 1.f, 0.f, rot != nullptr, {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}};
+    if (rot)
+        for (int k = 0; k < 9; ++k) c.r[k] = rot[k];
+    mesh_shade m{base_r, base_g, base_b, ambient, k_d, lx, ly, lz};
+    mesh_draw_targets tg{(const whmr_render_draw*)draws, (const whmr_render_image*)images, R, NI, verts1 != nullptr, total_pixels};
+    mesh_scene sc{(const whmr_ground_row*)grounds, heights, ground_out, ground_y, D};
+    mesh_marks mk{(const whmr_style_row*)styles, (const whmr_skeleton_row*)skeletons, bones, bone_rgb, joint_rgb, joints, keypoints, kp_out, overlay_out,
+                  S, NB, J, R};
+    long n0 = (long)D * V > total_pixels ? (long)D * V : total_pixels;                      // >= D
+    if ((long)S * J > n0) n0 = (long)S * J;
+    hipLaunchKernelGGL(mesh_marked_vertex_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, verts0, verts1, faces, vf_ptr, vf_idx, cam_t, focal, scr,
+                       nrm, (unsigned long long*)zbuf, D, V, tg, c, heights, mk, znear);
+    WHMR_CHECK_LAUNCH();
+    if (D > 0) {
+        const long n1 = (long)D * (F > V ? F : V);
+        hipLaunchKernelGGL(mesh_scene_faces_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, verts0, verts1, scr, faces, (unsigned long long*)zbuf,
+                           V, F, znear, tg, sc);
+        WHMR_CHECK_LAUNCH();
+    }
+    const long mean_plane = (total_pixels + NI - 1) / NI;
+    hipLaunchKernelGGL(mesh_marked_resolve_kernel, dim3((unsigned)((mean_plane + 255) / 256), (unsigned)NI), dim3(256), 0, st, scr, nrm, faces,
+                       (const unsigned long long*)zbuf, color_out, face_out, depth_out, cam_t, focal, V, F, znear, tg, m, c, sc, mk);
     WHMR_CHECK_LAUNCH();
     return 0;
 }

@@ -111,40 +111,85 @@ def infer_frame(model, frame_u8, dets, with_full_image=True, full_image='torch')
                  orig_shape=kw['orig_shape'], bbox_info=kw['bbox_info'], is_train=False, J_regressor=None, full_x=kw['full_x'])
 
 
+def _smpl_of(model):
+    return model.regressor[0].smpl
+
+
 @torch.no_grad()
-def render_frame(out, frame_u8, renderer, per_person=False, ground=False):
+def keypoints_full_image(model, out, sizes, frame_index=None):
+    """The [P, 49, 3] keypoints (x, y, 1) of the vis_dict ``out`` in full-image pixels, which WHMR.forward does not return at inference: the 49
+    joints of ``local_smpl_vertices`` (``SMPL.joints_from_vertices`` of the model's SMPL, so smoothed rows give smoothed keypoints) through the camera
+    the overlay is drawn with -- ``pred_cam_t``, ``focal_length``, identity rotation, the frame centre (W // 2, H // 2) (tester.py:185,194).  sizes:
+    (H, W) of the frame, or with frame_index (HOST integers, the frame of every row) one (H, W) per frame.  The third column is the confidence the
+    ``keypoints_2d`` arguments of the renderer read: a prediction has none, so 1."""
+    verts = out['local_smpl_vertices']
+    P = verts.shape[0]
+    if frame_index is None:
+        per_row = [(int(sizes[0]), int(sizes[1]))] * P
+    else:
+        index = [int(i) for i in np.asarray(frame_index.cpu() if torch.is_tensor(frame_index) else frame_index).reshape(-1)]
+        if len(index) != P:
+            raise ValueError('%d rows but %d frame indices' % (P, len(index)))
+        per_row = [(int(sizes[i][0]), int(sizes[i][1])) for i in index]
+    joints = _smpl_of(model).joints_from_vertices(verts)
+    center = torch.tensor([[w // 2, h // 2] for h, w in per_row], dtype=torch.float32).to(verts.device)
+    xy = L.perspective(joints, None, out['pred_cam_t'].float().reshape(P, 3), out['focal_length'].float().reshape(P), center)
+    return torch.cat([xy, torch.ones_like(xy[..., :1])], dim=2)
+
+
+def _marks(model, out, wireframe, draw_keypoints):
+    """the renderer's arguments for --wireframe / --draw_keypoints: the skeleton is that of the rows drawn, projected by the renderer itself"""
+    kw = {}
+    if wireframe:
+        kw['wireframe'] = True
+    if draw_keypoints:
+        if model is None:
+            raise ValueError('draw_keypoints needs the model: the joints come from its SMPL')
+        kw['joints'] = _smpl_of(model).joints_from_vertices(out['local_smpl_vertices'])
+    return kw
+
+
+@torch.no_grad()
+def render_frame(out, frame_u8, renderer, per_person=False, ground=False, wireframe=False, draw_keypoints=False, model=None, want=()):
     """The picture of a frame (tester.py:176-214, overlay panel): ``local_smpl_vertices`` of the vis_dict ``out`` drawn over ``frame_u8`` with
     ``pred_cam_t`` / ``focal_length``, identity camera rotation (tester.py:194) and the frame centre (:185) by ``renderer``
     (utils.renderer_cam.MeshRenderer).  uint8 [H, W, 3] with all persons in one depth buffer, or [P, H, W, 3] with per_person.  ground: True (or a
     height) puts the checkerboard ground plane under every person; a plane has one person's camera, so it needs per_person or a single person
-    (ValueError otherwise).  No host sync."""
+    (ValueError otherwise).  wireframe: the meshes as hidden-line wireframe (--wireframe, whmr_demo.py:152); draw_keypoints: every person's
+    keypoint skeleton under the mesh (--draw_keypoints, :158) -- the 49 joints of the rows drawn, from ``model``'s SMPL, so smoothed rows draw
+    smoothed skeletons.  want: as MeshRenderer.render (a dict comes back; 'keypoints' = the projected joints).  No host sync."""
     if isinstance(frame_u8, np.ndarray):
         frame_u8 = torch.from_numpy(np.ascontiguousarray(frame_u8)).cuda()
-    return renderer.render(frame_u8, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], per_person=per_person, ground=ground)
+    return renderer.render(frame_u8, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], per_person=per_person, ground=ground, want=want,
+                           **_marks(model, out, wireframe, draw_keypoints))
 
 
 @torch.no_grad()
-def render_clip(out, frames, renderer, frame_index, per_person=False, ground=False):
+def render_clip(out, frames, renderer, frame_index, per_person=False, ground=False, wireframe=False, draw_keypoints=False, model=None, want=()):
     """``render_frame`` for a whole clip in one launch group (MeshRenderer.render_clip): the rows of the vis_dict ``out`` drawn over their frames.
     frames: [F, H, W, 3] or a list of frames (device tensors; numpy is uploaded); frame_index: the frame of every row as HOST integers.  Returns a
     list of F uint8 images, each equal to ``render_frame`` on that frame's rows (a frame without rows: its own bytes), or P images with per_person.
-    ground as for ``render_frame``, in the same launch group."""
+    ground, wireframe, draw_keypoints (with ``model``) and want as for ``render_frame``, in the same launch group."""
     if isinstance(frames, np.ndarray):
         frames = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
     elif not torch.is_tensor(frames):
         frames = [torch.from_numpy(np.ascontiguousarray(f)).cuda() if isinstance(f, np.ndarray) else f for f in frames]
-    return renderer.render_clip(frames, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], frame_index, per_person=per_person, ground=ground)
+    return renderer.render_clip(frames, out['local_smpl_vertices'], out['pred_cam_t'], out['focal_length'], frame_index, per_person=per_person, ground=ground,
+                                want=want, **_marks(model, out, wireframe, draw_keypoints))
 
 
 class FramePipeline:
     """infer_frame with the model call (cam_model + W-HMR forward, ~200 launches) replayed from a HIP graph per (number of persons,
     full-image size): at one to a few persons per frame the eager path is bound by Python launch overhead, not by the GPU.
     With ``renderer`` (utils.renderer_cam.MeshRenderer) the call returns (vis_dict, image): the overlay is launched right behind the replayed graph on
-    the same stream, with no host sync between model and picture; ``ground`` is handed to ``render_frame``."""
+    the same stream, with no host sync between model and picture; ``ground``, ``wireframe``, ``draw_keypoints`` and ``want`` are handed to
+    ``render_frame`` (with ``want`` the second value is the renderer's dict: 'image', 'keypoints', ...)."""
 
-    def __init__(self, model, with_full_image=True, renderer=None, per_person=False, full_image='torch', ground=False):
+    def __init__(self, model, with_full_image=True, renderer=None, per_person=False, full_image='torch', ground=False, wireframe=False,
+                 draw_keypoints=False, want=()):
         self.model, self.with_full_image, self._graphs = model, with_full_image, {}
         self.renderer, self.per_person, self.full_image, self.ground = renderer, per_person, full_image, ground
+        self.wireframe, self.draw_keypoints, self.want = wireframe, draw_keypoints, tuple(want)
 
     @torch.no_grad()
     def __call__(self, frame_u8, dets):
@@ -161,7 +206,7 @@ class FramePipeline:
         out = g(**call)
         if self.renderer is None:
             return out
-        return out, render_frame(out, frame_u8, self.renderer, self.per_person, self.ground)
+        return out, render_frame(out, frame_u8, self.renderer, self.per_person, self.ground, self.wireframe, self.draw_keypoints, self.model, self.want)
 
 
 # ----------------------------------------------------------------------------- clip inference: all persons of many frames in one model call
@@ -272,11 +317,14 @@ class ClipPipeline:
     ``render_clip`` launch group for the whole clip, each image what ``render_frame`` draws over that frame's rows, behind the replayed graph on the
     same stream, no host sync; a frame without detections comes back as a copy of itself; per_person: [P images], one person each.  With
     ``smoother`` (a TrackSmoother) and per-call ``track_ids`` the smoothing stage (one filter launch + two SMPL calls) runs behind the replayed graph on the same stream, outside the graph -- its table changes per clip, like the input preparation --
-    and the renderer draws the smoothed rows; the padding rows never enter a track.  ``ground`` is handed to ``render_clip``."""
+    and the renderer draws the smoothed rows; the padding rows never enter a track.  ``ground``, ``wireframe``, ``draw_keypoints`` and ``want`` are handed
+    to ``render_clip``: the skeletons are those of the rows drawn, smoothed ones included."""
 
-    def __init__(self, model, with_full_image=True, person_bucket=8, renderer=None, smoother=None, per_person=False, ground=False):
+    def __init__(self, model, with_full_image=True, person_bucket=8, renderer=None, smoother=None, per_person=False, ground=False, wireframe=False,
+                 draw_keypoints=False, want=()):
         self.model, self.with_full_image, self.person_bucket, self.renderer, self._graphs = model, with_full_image, person_bucket, renderer, {}
         self.smoother, self.per_person, self.ground = smoother, per_person, ground
+        self.wireframe, self.draw_keypoints, self.want = wireframe, draw_keypoints, tuple(want)
 
     @torch.no_grad()
     def __call__(self, frames, dets_per_frame, track_ids=None):
@@ -297,7 +345,8 @@ class ClipPipeline:
         if self.renderer is None:
             return out
         index = np.repeat(np.arange(len(dets_per_frame)), [len(d) for d in dets_per_frame])       # from the detections: the host has them
-        return out, render_clip(out, kw['frames'], self.renderer, index, self.per_person, self.ground)
+        return out, render_clip(out, kw['frames'], self.renderer, index, self.per_person, self.ground, self.wireframe, self.draw_keypoints, self.model,
+                                self.want)
 
 
 # ----------------------------------------------------------------------------- temporal smoothing of tracked persons

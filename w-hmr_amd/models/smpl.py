@@ -163,6 +163,25 @@ class SMPL(nn.Module):
             L.smpl_stage_tail(m, verts, pj, joints, sj, mk, csr=self._dev_cache[2]['csr'] if self.csr_tail else None)
         return ModelOutput(verts, joints, sj, rot, aa, mk, tail)
 
+    @torch.no_grad()
+    def joints_from_vertices(self, verts):
+        """verts [P, 6890, 3] -> the 49 named joints [P, 49, 3] of a mesh whose pose is not at hand (smoothed or loaded vertices; the demo's keypoint
+        skeleton): two calls of the whmr_smpl_joints launch pair.  The 24 kinematic joints are regressed from the posed vertices (J_regressor .
+        verts, smplx's vertices2joints) -- the forward pass takes them from the kinematic chain instead, a few millimetres away -- the vertex
+        joints and the 9 extra regressed joints are the forward pass's own."""
+        if not verts.is_cuda:
+            raise RuntimeError('whmr_amd.SMPL runs on a HIP device only (no CPU fallback)')
+        verts = verts.float().contiguous()
+        P = verts.shape[0]
+        if verts.dim() != 3 or tuple(verts.shape[1:]) != (self.NUM_VERTS, 3) or P < 1:
+            raise ValueError('verts is [P, %d, 3] with P >= 1, got %s' % (self.NUM_VERTS, tuple(verts.shape)))
+        m = self._model()
+        sj = torch.empty(P, 45, 3, dtype=torch.float32, device=verts.device)
+        L.smpl_joints(m, verts, None, None, sj, None)
+        joints = torch.empty(P, 49, 3, dtype=torch.float32, device=verts.device)
+        L.smpl_joints(m, verts, sj[:, :24].contiguous(), joints, None, None)
+        return joints
+
     def forward(self, betas=None, body_pose=None, global_orient=None, pose2rot=False, **kwargs):
         """pare.models.SMPL.forward call shape (whmr.py:132-137).  pose2rot=True takes axis-angle [B,69] / [B,3]."""
         if pose2rot:
